@@ -12,11 +12,15 @@ processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per GPU, RC
 touches the GPU, relays rank 0's JSON line and exits non-zero if any rank fails (launch_ranks). `n_gpus` in the line is the
 number of ranks that answered a 1-element SUM all-reduce, not the flag.
 
-Prints ONE JSON line on rank 0. Extra objects:
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps and prints the headline figures. With
+--full the line also carries what takes runs of its own, measured after the timed steps: generator_fwd_* (generator forward
+latencies), roofline_short_k (the critic's conv2) and
   roofline      dominant kernel (the fp16 MFMA implicit-GEMM transposed conv on the u3 shape), timed live
                 with HIP events on the kernel's stream: algorithmic FLOP / average launch time vs 2.5 PFLOP/s
   cpu_baseline  the CPU oracle (port of the reference's torch path) on this host's cores, bounded sample
   --kernel-only runs just the dominant-kernel launches (what profiles/*kernel* summarises with rocprofv3).
+  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB; seeded inputs, so two
+  builds run with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -203,6 +207,44 @@ def critic_conv2_kernel(iters):
                 ms=ms.value, flop=flop, bytes=(x.numel() + packed.numel() + out.numel()) * 2)
 
 
+def generator_forward_latencies(G, batch, reps=20):
+    """Generator forward latency (train-mode forward as inside the loop), HIP events on the compute stream; then the same in
+    eval mode and in inference mode. Leaves G in train mode."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    g, m = batch
+    masked = g * (1 - m)
+    for _ in range(3):
+        G._forward_raw(masked)
+    e0.record()
+    for _ in range(reps):
+        G._forward_raw(masked)
+    e1.record()
+    torch.cuda.synchronize()
+    gen_fwd_ms = e0.elapsed_time(e1) / reps
+    # the same in eval mode (running-statistics BatchNorm, no dropout): what eval.py / the evaluation pass run
+    G.eval()
+    for _ in range(3):
+        G._forward_raw(masked)
+    e0.record()
+    for _ in range(reps):
+        G._forward_raw(masked)
+    e1.record()
+    torch.cuda.synchronize()
+    gen_fwd_eval_ms = e0.elapsed_time(e1) / reps
+    # inference: eval mode, never differentiated -> BatchNorm folded into the convolutions (gi_net_set_inference)
+    for _ in range(3):
+        G._forward_raw(masked, inference=True)
+    e0.record()
+    for _ in range(reps):
+        G._forward_raw(masked, inference=True)
+    e1.record()
+    torch.cuda.synchronize()
+    gen_fwd_inf_ms = e0.elapsed_time(e1) / reps
+    G.train()
+    return {"generator_fwd_ms": gen_fwd_ms, "generator_fwd_eval_ms": gen_fwd_eval_ms, "generator_fwd_inference_ms": gen_fwd_inf_ms,
+            "generator_fwd_mfma_frac": BS * F_G / (gen_fwd_ms * 1e-3) / (PEAK_F16_TFLOPS * 1e12)}
+
+
 def roofline_of(k, dtype="fp16", traffic=None, traffic_src=None):
     peak = PEAK_F16_TFLOPS if dtype == "fp16" else PEAK_F32_TFLOPS
     achieved = k["flop"] / (k["ms"] * 1e-3) / 1e12
@@ -288,6 +330,40 @@ def cpu_baseline(workload="wgan_rmse_256", full=True):
                        f"{sorted(sweep)} threads): {warm} warm-up + {0 if dual else nc} critic-only batches ({t[0]:.2f} s each) + {ng} "
                        f"batch(es) with G update ({t[1]:.2f} s), weighted {G_EVERY - 1}:1" + ("" if full else " (reduced sample: secondary workload)"),
                 sweep={str(k): round(sweep[k], 3) for k in sorted(sweep)})
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22       # tensors with more elements are written as a fixed seeded sample of this many
+
+
+def dump_outputs(dirname, arrays):
+    """{name: tensor} -> dirname/<name>.npy in float32 (after the timed steps; the caller has synchronised)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0x0D5A)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs to dump: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench.py: wrote {len(out)} arrays ({total / 2**20:.1f} MB) to {dirname}", file=sys.stderr)
+
+
+def step_outputs(step, nets):
+    """What a caller of one training step receives: the loss terms, the inpainted batch and the updated networks (fp32
+    master weights; buffers = BatchNorm running statistics)."""
+    arrays = {f"loss_{k}": v for k, v in step.L.items()}
+    arrays["inpainted"] = step.inpainted
+    for name, net in nets.items():
+        arrays[f"{name}_params"] = net.flat_params()
+        arrays[f"{name}_buffers"] = torch.cat([b.reshape(-1) for b in net.buffers() if b.is_floating_point()])
+    return arrays
 
 
 def ssim_workload(args, dev):
@@ -415,7 +491,14 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--short-k", action="store_true", help="with --kernel-only: the critic's conv2 (roofline_short_k) instead of the dominant kernel")
     ap.add_argument("--kernel-iters", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: generator forward latencies, the rooflines of "
+                         "the dominant kernels, the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.kernel_only or args.workload in ("rehearsal", "ssim_256", "vgg_512", "dual_d_256")):
+        ap.error("--dump-outputs needs a training workload (wgan_rmse_256, wgan_gp_128, config5_512)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -518,6 +601,8 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:    # before anything else runs on the networks (the --full forward timing moves BatchNorm statistics)
+        dump_outputs(args.dump_outputs, step_outputs(step, {"generator": G, "critic": D}))
     if c5:   # secondary workload: its dominant kernel is the same transposed convolution at 512x512 / bs=8 (u3: 64x64 maps)
         line = {"metric": "training images/sec at 512x512 bs=8/GPU (wgan_perceptual_style_faceparsing)",
                 "value": alive * BS * args.steps / dt, "unit": "images/sec", "n_gpus": alive, "steps": args.steps,
@@ -542,51 +627,6 @@ def main():
             line["cpu_baseline"] = cpu_baseline("wgan_gp_128", full=False)
         print(json.dumps(line))
         return
-    # generator forward latency (train-mode forward as inside the loop), HIP events on the compute stream
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    g, m = batches[0]
-    masked = g * (1 - m)
-    for _ in range(3):
-        G._forward_raw(masked)
-    e0.record()
-    reps = 20
-    for _ in range(reps):
-        G._forward_raw(masked)
-    e1.record()
-    torch.cuda.synchronize()
-    gen_fwd_ms = e0.elapsed_time(e1) / reps
-    # the same in eval mode (running-statistics BatchNorm, no dropout): what eval.py / the evaluation pass run
-    G.eval()
-    for _ in range(3):
-        G._forward_raw(masked)
-    e0.record()
-    for _ in range(reps):
-        G._forward_raw(masked)
-    e1.record()
-    torch.cuda.synchronize()
-    gen_fwd_eval_ms = e0.elapsed_time(e1) / reps
-    # inference: eval mode, never differentiated -> BatchNorm folded into the convolutions (gi_net_set_inference)
-    for _ in range(3):
-        G._forward_raw(masked, inference=True)
-    e0.record()
-    for _ in range(reps):
-        G._forward_raw(masked, inference=True)
-    e1.record()
-    torch.cuda.synchronize()
-    gen_fwd_inf_ms = e0.elapsed_time(e1) / reps
-    G.train()
-
-    k = dominant_kernel(args.kernel_iters)
-    traffic, traffic_src = None, None
-    tp = os.path.join(ROOT, "profiles", "dominant_kernel_traffic.json")
-    if os.path.exists(tp):
-        try:
-            tj = json.load(open(tp))
-            traffic = tj.get("hbm_bytes_per_launch")
-            # the PMC passes are separate rocprofv3 runs (tools/pmc_dominant.sh): say which round's file this number is
-            traffic_src = f"profiles/dominant_kernel_traffic.json (round {tj.get('round')}, kernel {tj.get('kernel')}, commit {tj.get('commit')})"
-        except Exception:
-            traffic = None
     # algorithmic FLOP of one batch: D-only = F_G + 6 F_D ; with G update + 2 F_G + 2 F_D
     flop_batch = BS * ((F_G + 6 * F_D) + (2 * F_G + 2 * F_D) / G_EVERY)
     out = {
@@ -606,14 +646,26 @@ def main():
                                "RMSprop 5e-5, clip 0.01, RMSE recon, G update every 5th batch, random-init weights",
                    "global_batch": world * BS, "parallelism": f"dp{world}",
                    "compute": "fp16 MFMA, fp32 accumulate, fp32 master weights" if args.dtype == "fp16" else "fp32 MFMA"},
-        "generator_fwd_ms": gen_fwd_ms,
-        "generator_fwd_eval_ms": gen_fwd_eval_ms,
-        "generator_fwd_inference_ms": gen_fwd_inf_ms,
-        "generator_fwd_mfma_frac": BS * F_G / (gen_fwd_ms * 1e-3) / (PEAK_F16_TFLOPS * 1e12),
-        "step_algorithmic_tflops": flop_batch / (dt / args.steps) / 1e12,
-        "losses": losses,
-        "roofline": roofline_of(k, "fp16" if args.dtype == "fp16" else "fp32", traffic, traffic_src),
     }
+    if args.full:
+        out.update(generator_forward_latencies(G, batches[0]))
+    out["step_algorithmic_tflops"] = flop_batch / (dt / args.steps) / 1e12
+    out["losses"] = losses
+    if not args.full:
+        print(json.dumps(out))
+        return
+    k = dominant_kernel(args.kernel_iters)
+    traffic, traffic_src = None, None
+    tp = os.path.join(ROOT, "profiles", "dominant_kernel_traffic.json")
+    if os.path.exists(tp):
+        try:
+            tj = json.load(open(tp))
+            traffic = tj.get("hbm_bytes_per_launch")
+            # the PMC passes are separate rocprofv3 runs (tools/pmc_dominant.sh): say which round's file this number is
+            traffic_src = f"profiles/dominant_kernel_traffic.json (round {tj.get('round')}, kernel {tj.get('kernel')}, commit {tj.get('commit')})"
+        except Exception:
+            traffic = None
+    out["roofline"] = roofline_of(k, "fp16" if args.dtype == "fp16" else "fp32", traffic, traffic_src)
     if args.dtype == "fp16":   # the short-K layer family with the most kernel time of the benchmark, beside the dominant kernel
         t2, t2_src = None, None
         tp2 = os.path.join(ROOT, "profiles", "short_k_kernel_traffic.json")

@@ -9,7 +9,7 @@ mkdir -p $OUT
 for round in 1 2; do
   for v in $A $B; do
     echo "== $OPT=$v round $round"
-    env $OPT=$v python3 $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>$OUT/bench_err.log | python3 -c "
+    env $OPT=$v python3 $R/bench.py --steps 40 --warmup 5 --full --no-cpu-baseline 2>$OUT/bench_err.log | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('headline', d['value'], d['ms_per_step'], d.get('generator_fwd_ms'), d['roofline']['frac'])"

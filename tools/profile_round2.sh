@@ -14,7 +14,7 @@ run() { name=$1; shift; echo "== $name"; timeout -k 10 600 "$@" > $OUT/$name.log
 if [ "$PART" != "2" ]; then
 # A. the dominant kernel alone; B. the whole benchmark process; C. its HBM traffic (one --pmc pass per counter)
 run kernel_only rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kernel_only -- python3 $R/bench.py --kernel-only --kernel-iters 50
-run bench rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --steps 20 --warmup 5 --preheat 50 --no-cpu-baseline
+run bench rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -- python3 $R/bench.py --steps 20 --warmup 5 --preheat 50 --full --no-cpu-baseline
 run pmc_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $R/bench.py --kernel-only --kernel-iters 10
 run pmc_write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $R/bench.py --kernel-only --kernel-iters 10
 # D. counters of the dominant kernel
@@ -42,8 +42,8 @@ for wl in wgan_gp_128 dual_d_256 config5_512 vgg_512; do
 done
 # G. the headline line itself, unprofiled (with the CPU baseline); H. the multi-rank launch path rehearsed with two gloo ranks on
 # this one card (RCCL needs one GPU per rank: the 8-GPU run is the driver's)
-run line_headline python3 $R/bench.py --steps 20 --warmup 5
-GI_DIST_BACKEND=gloo run line_two_ranks_gloo python3 $R/bench.py --gpus 2 --steps 10 --warmup 2 --preheat 20 --no-cpu-baseline
+run line_headline python3 $R/bench.py --steps 20 --warmup 5 --full
+GI_DIST_BACKEND=gloo run line_two_ranks_gloo python3 $R/bench.py --gpus 2 --steps 10 --warmup 2 --preheat 20 --full --no-cpu-baseline
 # I. per-layer / per-instantiation table of the GEMM-shaped launches (HIP events, no profiler)
 run layer_table python3 $R/tools/layer_table.py $TAG 30
 fi

@@ -10,7 +10,7 @@ $R/tools/fwd_ab.sh ${TAG} GI_LIB_PATH=$BASE GI_LIB_PATH=$NEW 2>&1 | tee $OUT/fwd
 for round in 1 2; do
   for lib in $BASE $NEW; do
     echo "== bench $(basename $lib) round $round"
-    GI_LIB_PATH=$lib python3 $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>$OUT/bench_err.log | python3 -c "
+    GI_LIB_PATH=$lib python3 $R/bench.py --steps 40 --warmup 5 --full --no-cpu-baseline 2>$OUT/bench_err.log | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d.get('generator_fwd_ms'), d['roofline']['frac'], d.get('roofline_short_k',{}).get('frac'))"

@@ -43,7 +43,7 @@ with open(f"profiles/{tag}_summary.md", "w") as out:
               "(`igemm_kernelIDF16_Li1E...` = `igemm_kernel<_Float16, PHASE=1, BM, BN, WGM, WGN>`).\n\n")
     ko = stats(newest(f"{src}/kernel_only/runc/*_kernel_stats.csv"),
                "A. `python bench.py --kernel-only --kernel-iters 50` — the dominant kernel alone (the roofline object's launch)", out)
-    stats(newest(f"{src}/bench/runc/*_kernel_stats.csv"), "B. `python bench.py --steps 10 --warmup 5 --no-cpu-baseline` — whole benchmark process", out)
+    stats(newest(f"{src}/bench/runc/*_kernel_stats.csv"), "B. `python bench.py --steps 10 --warmup 5 --full --no-cpu-baseline` — whole benchmark process", out)
     fetch, nf = pmc(newest(f"{src}/pmc_fetch/runc/*_counter_collection.csv"), "FETCH_SIZE")
     write, nw = pmc(newest(f"{src}/pmc_write/runc/*_counter_collection.csv"), "WRITE_SIZE")
     dom = [r for r in ko if ("igemm5_kernel" in r["Name"] or "igemm3_kernel" in r["Name"])][0]

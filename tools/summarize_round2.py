@@ -92,7 +92,7 @@ with open(f"profiles/{tag}_summary.md", "w") as out:
     ko = stats_table(p, "A. `python bench.py --kernel-only --kernel-iters 50`: the dominant kernel alone (the roofline object's launch)", out, 6)
     copy_stats(p, f"profiles/{tag}_kernel_only_kernel_stats.csv")
     p = newest(f"{src}/bench/*/*_kernel_stats.csv")
-    stats_table(p, "B. `python bench.py --steps 20 --warmup 5 --preheat 50 --no-cpu-baseline`: the whole benchmark process (includes the generator-forward and "
+    stats_table(p, "B. `python bench.py --steps 20 --warmup 5 --preheat 50 --full --no-cpu-baseline`: the whole benchmark process (includes the generator-forward and "
                    "dominant-kernel timing loops bench.py runs after the timed steps)", out)
     copy_stats(p, f"profiles/{tag}_bench_kernel_stats.csv")
     dom = [r for r in ko if DOM in r["Name"]][0]
