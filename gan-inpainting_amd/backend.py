@@ -61,6 +61,7 @@ PROTOTYPES = {
     "gi_net_allreduce_grads_async": (_i, [_vp, _vp, _i64, _i64, _vp]),
     "gi_allreduce_wait": (_i, [_vp, _vp, _vp]),
     "gi_patchgan_gradient_penalty": (_i, [_vp, _vp, _i, _f, _vp]),
+    "gi_patchgan_gp_saved_activation": (_i, [_vp, _i, _vp, _i64]),
     "gi_interpolate": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "gi_mask_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i]),
     "gi_mask_composite": (_i, [_vp, _vp, _vp, _vp, _vp, _i64]),

@@ -454,5 +454,9 @@ int op_mask_nchw_to_nhwc(hipStream_t st, const uint8_t* src, uint8_t* dst, int n
 int op_mul_slope(hipStream_t st, int dtype, const void* tin, const void* a, void* tout, int64_t count);
 int op_bn_tangent_inject(hipStream_t st, int dtype, const void* dta, const void* y, const void* tx, const void* x, void* dxp,
                          int64_t pixels, int c, const float* gamma, const float* mean, const float* inv, float* dgamma,
-                         float* partials, float* sums);
-int op_gp_direction(hipStream_t st, const float* g, int n, int64_t hw, float lam, float* sumsq, float* v, float* penalty);
+                         float dgamma_scale, float* partials, float* sums);
+// v = s * d(penalty)/dg, s = 2^k per call (max|v| in [1, 2)), sc[0] = s, sc[1] = 1/s; sumsq / amax: n floats each
+int op_gp_direction(hipStream_t st, const float* g, int n, int64_t hw, float lam, float* sumsq, float* amax, float* v, float* penalty,
+                    float* sc);
+// dst += src * sc[1] (count floats)
+int op_gp_unscale_add(hipStream_t st, const float* src, const float* sc, float* dst, int64_t count);

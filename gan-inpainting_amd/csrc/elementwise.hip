@@ -934,7 +934,7 @@ struct InjP {
   const char* dta; const char* y; const char* tx; const char* x; char* dxp;   // dxp: += inj (in place on the primal gradient)
   int64_t pixels; int c;
   const float* gamma; const float* mean; const float* inv;
-  float* partials; const float* sums; float* dgamma;
+  float* partials; const float* sums; float* dgamma; float dgamma_scale;   // dgamma += dgamma_scale * A * inv
   int rows_per_block;
 };
 template <typename T>
@@ -1030,35 +1030,63 @@ __global__ void __launch_bounds__(256) bn_inject_apply_kernel(InjP p) {
   if (p.dgamma && blockIdx.x == 0) {
     for (int ch = threadIdx.x; ch < p.c; ch += 256) {
       const float Sa = p.sums[ch], Sax = p.sums[p.c + ch], St = p.sums[2 * p.c + ch], Stx = p.sums[3 * p.c + ch], Sat = p.sums[4 * p.c + ch];
-      p.dgamma[ch] += (Sat - Sa * St * invM - Sax * Stx * invM) * p.inv[ch];
+      p.dgamma[ch] += (Sat - Sa * St * invM - Sax * Stx * invM) * p.inv[ch] * p.dgamma_scale;
     }
   }
 }
 
-// per-sample squared L2 norm of g (n, hw) -> sumsq[n]
-__global__ void __launch_bounds__(256) sample_sumsq_kernel(const float* g, int64_t hw, float* sumsq) {
+// per-sample squared L2 norm of g (n, hw) -> sumsq[n], and its largest magnitude -> amax[n]
+__global__ void __launch_bounds__(256) sample_sumsq_kernel(const float* g, int64_t hw, float* sumsq, float* amax) {
   __shared__ double sh[4];
+  __shared__ float shm[4];
   const float* p = g + (int64_t)blockIdx.x * hw;
   double s = 0.0;
-  for (int64_t i = threadIdx.x; i < hw; i += 256) s += (double)p[i] * p[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  float m = 0.f;
+  for (int64_t i = threadIdx.x; i < hw; i += 256) { s += (double)p[i] * p[i]; m = fmaxf(m, fabsf(p[i])); }
+  for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); m = fmaxf(m, __shfl_xor(m, off)); }
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s; shm[threadIdx.x >> 6] = m; }
   __syncthreads();
-  if (threadIdx.x == 0) sumsq[blockIdx.x] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+  if (threadIdx.x == 0) {
+    sumsq[blockIdx.x] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+    amax[blockIdx.x] = fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]));
+  }
 }
 // v[n,:] = lam/N * 2 (||g_n|| - 1) / ||g_n|| * g[n,:] ; penalty = lam * mean_n (||g_n|| - 1)^2 (written by block 0)
-__global__ void __launch_bounds__(256) gp_direction_kernel(const float* g, const float* sumsq, int n, int64_t hw, float lam,
-                                                           float* v, float* penalty) {
-  const int nn = blockIdx.y;
+__device__ __forceinline__ float gp_coef(const float* sumsq, int nn, int n, float lam) {
   const float norm = sqrtf(sumsq[nn]);
-  const float coef = norm > 0.f ? lam / (float)n * 2.f * (norm - 1.f) / norm : 0.f;
+  return norm > 0.f ? lam / (float)n * 2.f * (norm - 1.f) / norm : 0.f;
+}
+// Tangent scale: the direction is written as v * s with ONE power of two s = 2^k per call, chosen from
+// max|v| = max_n |coef_n| * amax_n so that max|v * s| lies in [1, 2): the fp16 tangent forward then runs in the normal range
+// whatever lam and ||g_n|| - 1 are. s = 1 when v is zero or not finite (lam = 0, every ||g_n|| = 1; an overflow stays visible).
+// Every block derives s from the same n values in the same order; block (0, 0) stores sc[0] = s, sc[1] = 1/s (both exact).
+__global__ void __launch_bounds__(256) gp_direction_kernel(const float* g, const float* sumsq, const float* amax, int n, int64_t hw,
+                                                           float lam, float* v, float* penalty, float* sc) {
+  const int nn = blockIdx.y;
+  float vmax = 0.f;
+  for (int k = 0; k < n; ++k) vmax = fmaxf(vmax, fabsf(gp_coef(sumsq, k, n, lam)) * amax[k]);
+  int e = (vmax > 0.f && isfinite(vmax)) ? -ilogbf(vmax) : 0;
+  e = e < -126 ? -126 : (e > 126 ? 126 : e);
+  const float s = ldexpf(1.f, e);
+  const float coef = gp_coef(sumsq, nn, n, lam);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256)
-    v[(int64_t)nn * hw + i] = coef * g[(int64_t)nn * hw + i];
-  if (penalty && blockIdx.x == 0 && nn == 0 && threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < n; ++k) { const double d = sqrt((double)sumsq[k]) - 1.0; s += d * d; }
-    penalty[0] = (float)(lam * s / n);
+    v[(int64_t)nn * hw + i] = (coef * g[(int64_t)nn * hw + i]) * s;
+  if (blockIdx.x == 0 && nn == 0 && threadIdx.x == 0) {
+    sc[0] = s;
+    sc[1] = ldexpf(1.f, -e);
+    if (penalty) {
+      double acc = 0.0;
+      for (int k = 0; k < n; ++k) { const double d = sqrt((double)sumsq[k]) - 1.0; acc += d * d; }
+      penalty[0] = (float)(lam * acc / n);
+    }
   }
+}
+// dst[i] += src[i] * sc[1]: the penalty's parameter gradients (accumulated at tangent scale s in a private buffer) into the bound
+// gradients, one fixed-order add per element
+__global__ void __launch_bounds__(256) gp_unscale_add_kernel(const float* __restrict__ src, const float* __restrict__ sc, float* __restrict__ dst,
+                                                             int64_t count) {
+  const float is = sc[1];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) dst[i] += src[i] * is;
 }
 // out[n,:] = fake[n,:] + eps[n] * (real[n,:] - fake[n,:])
 __global__ void __launch_bounds__(256) interpolate_kernel(const float* real, const float* fake, const float* eps, int64_t hw,
@@ -1766,13 +1794,14 @@ int op_mul_slope(hipStream_t st, int dtype, const void* tin, const void* a, void
 
 int op_bn_tangent_inject(hipStream_t st, int dtype, const void* dta, const void* y, const void* tx, const void* x, void* dxp,
                          int64_t pixels, int c, const float* gamma, const float* mean, const float* inv, float* dgamma,
-                         float* partials, float* sums) {
+                         float dgamma_scale, float* partials, float* sums) {
   const int epc = dtype == GI_F16 ? 8 : 4;
   const int Q = c / epc;
   GI_REQUIRE(c % epc == 0 && gi_is_pow2(Q) && Q <= 256, "bn_tangent_inject: c=%d unsupported", c);
   InjP p;
   p.dta = (const char*)dta; p.y = (const char*)y; p.tx = (const char*)tx; p.x = (const char*)x; p.dxp = (char*)dxp;
   p.pixels = pixels; p.c = c; p.gamma = gamma; p.mean = mean; p.inv = inv; p.partials = partials; p.sums = sums; p.dgamma = dgamma;
+  p.dgamma_scale = dgamma_scale;
   int blocks = 0;
   p.rows_per_block = rows_per_block_for(pixels, &blocks);
   if (dtype == GI_F16) hipLaunchKernelGGL(bn_inject_reduce_kernel<half_t>, dim3(blocks), dim3(256), 0, st, p);
@@ -1787,10 +1816,17 @@ int op_bn_tangent_inject(hipStream_t st, int dtype, const void* dta, const void*
   return GI_OK;
 }
 
-int op_gp_direction(hipStream_t st, const float* g, int n, int64_t hw, float lam, float* sumsq, float* v, float* penalty) {
-  hipLaunchKernelGGL(sample_sumsq_kernel, dim3(n), dim3(256), 0, st, g, hw, sumsq);
+int op_gp_direction(hipStream_t st, const float* g, int n, int64_t hw, float lam, float* sumsq, float* amax, float* v, float* penalty,
+                    float* sc) {
+  hipLaunchKernelGGL(sample_sumsq_kernel, dim3(n), dim3(256), 0, st, g, hw, sumsq, amax);
   GI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gp_direction_kernel, dim3(nblocks(hw) > 64 ? 64 : nblocks(hw), n), dim3(256), 0, st, g, sumsq, n, hw, lam, v, penalty);
+  hipLaunchKernelGGL(gp_direction_kernel, dim3(nblocks(hw) > 64 ? 64 : nblocks(hw), n), dim3(256), 0, st, g, sumsq, amax, n, hw, lam, v, penalty, sc);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+
+int op_gp_unscale_add(hipStream_t st, const float* src, const float* sc, float* dst, int64_t count) {
+  hipLaunchKernelGGL(gp_unscale_add_kernel, dim3(nblocks(count)), dim3(256), 0, st, src, sc, dst, count);
   GI_LAUNCH_CHECK();
   return GI_OK;
 }

@@ -145,6 +145,7 @@ struct gi_net {
   // gradient-penalty scratch (patchgan): stacked 2n tensors, see patchgan_gradient_penalty
   int64_t oA2[5] = {-1, -1, -1, -1, -1}, oG2[5] = {-1, -1, -1, -1, -1}, oTX[5] = {-1, -1, -1, -1, -1};
   int64_t oD2 = -1, oTZ = -1, oGimg = -1, oVimg = -1, oGPs = -1, oGPpart = -1, oGPsums = -1, oTh = -1;
+  int64_t oGPgrad = -1;              // n_params floats: the penalty's parameter gradients at tangent scale, before the 1/s add
   int gp_slot = -1;
   std::vector<int> slot_n, slot_train, slot_groups;
   std::vector<std::vector<const uint8_t*>> ext_mask;  // [slot][level]
@@ -446,15 +447,16 @@ extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int ma
   if (maxSplit > 0) maxSplit = max64(maxSplit, (int64_t)400 * 128 * 128 * 4);
   net->split_bytes = maxSplit;
   net->oSplit = A.take(maxSplit > 0 ? maxSplit : 16);
-  for (int i = 2; i <= 4; ++i)
-    net->wg_bytes = max64(net->wg_bytes, op_wgrad_scratch_bytes(dtype, max_n, H >> i, W >> i, net->dconv[i].ca, net->dconv[i].cb));
+  for (int i = 2; i <= 4; ++i)   // 2 * max_n: the gradient penalty's stacked weight gradients (fixed-order split reduction there too)
+    for (int m : {max_n, 2 * max_n})
+      net->wg_bytes = max64(net->wg_bytes, op_wgrad_scratch_bytes(dtype, m, H >> i, W >> i, net->dconv[i].ca, net->dconv[i].cb));
   if (net->wg_bytes > 0) net->oWg = A.take(net->wg_bytes);
   net->oDh = A.take(N * net->P * 4);
   net->hw_bytes = op_head_scratch_bytes((int)N, net->Hh, net->Wh);
   net->oHw = A.take(net->hw_bytes);
   if (net->Hh * net->Wh > 256) { net->ht_bytes = N * net->Hh * net->Wh * 16 * 4; net->oHt = A.take(net->ht_bytes); }
   net->oCol = A.take(N * (H / 2) * (W / 2) * 16 * 2);
-  {   // gradient penalty (fp32 critics): tangent / stacked-gradient tensors
+  {   // gradient penalty: tangent / stacked-gradient tensors (compute type), its private gradient buffer
     int64_t maxl = 0;
     for (int i = 1; i <= 4; ++i) {
       const int64_t e = N * (H >> i) * (W >> i) * chans[i] * T;
@@ -467,7 +469,8 @@ extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int ma
     net->oTZ = A.take(maxl);
     net->oGimg = A.take(N * H * W * 4);
     net->oVimg = A.take(N * H * W * 4);
-    net->oGPs = A.take((N + 16) * 4 * 2);
+    net->oGPs = A.take((N + 16) * 4 * 4);   // ones | sumsq | amax | tangent scale s, 1/s
+    net->oGPgrad = A.take(net->n_params * 4);
     net->oGPpart = A.take((int64_t)1100 * 5 * 512 * 4);
     net->oGPsums = A.take(5 * 512 * 4);
     net->oTh = A.take(N * net->P * 4 * 2);
@@ -1741,13 +1744,18 @@ namespace {
 // couples the tangent to the PRIMAL activations through the batch statistics, which injects a primal
 // gradient at every norm layer (op_bn_tangent_inject). Tangent-side and primal-side gradients are
 // stacked as a 2n batch so every layer needs one input-gradient GEMM and one weight-gradient GEMM.
+// Scaling, both dtypes: the tangent forward runs on v * s (s = 2^k derived on the device, op_gp_direction) and
+// the reverse pass is seeded with the loss scale L. Tangent-side gradients (stacked half 0) then carry L, primal-side ones
+// (half 1) s * L, and every parameter-gradient product - stacked wgrad, conv1's two halves, the head's dw5 / dwl, dgamma of
+// the inject pass, dgamma / dbeta of the primal BatchNorm backward - carries s * L. The kernels remove L where they write fp32
+// as in every backward; the gradients land in a private buffer that one fixed-order pass adds into the bound ones times 1/s.
 int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, float* penalty_out) {
   hipStream_t st = net->ctx->stream;
   const int dt = net->dtype, H = net->H, W = net->W, s = net->gp_slot;
-  GI_REQUIRE(dt == GI_F32, "gradient_penalty: built for fp32 critics (BASELINE config 2); fp16 needs tangent scaling");
   GI_REQUIRE(!net->sigmoid && net->train, "gradient_penalty: needs a train-mode critic without sigmoid");
   GI_REQUIRE(net->bn_groups == 1, "internal: gradient_penalty runs with one BatchNorm group");
-  const int64_t T = 4;
+  const int64_t T = (int64_t)net->tsz();
+  const float LS = net->loss_scale, iLS = 1.f / LS;
   const int chans[5] = {1, 64, 128, 256, 512};
   auto A2 = [&](int i, int half) { return (void*)(net->shared(net->oA2[i]) + (int64_t)half * n * (H >> i) * (W >> i) * chans[i] * T); };
   auto G2 = [&](int i, int half) { return (void*)(net->shared(net->oG2[i]) + (int64_t)half * n * (H >> i) * (W >> i) * chans[i] * T); };
@@ -1755,16 +1763,25 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
   float* vimg = (float*)net->shared(net->oVimg);
   float* ones = (float*)net->shared(net->oGPs);
   float* sumsq = ones + (n + 16);
+  float* amax = sumsq + (n + 16);
+  float* sc = amax + (n + 16);   // s, 1/s
   float* th = (float*)net->shared(net->oTh);
   float* dth = th + (int64_t)n * net->P;
   float* ytmp = sumsq;   // (n) critic outputs, overwritten by sumsq afterwards
   // 1) primal forward + frozen backward: g = d(sum D)/dx
   GI_TRY(patchgan_forward(net, s, xhat, ytmp, n));
+  GI_REQUIRE(!net->slot_fused_u2[s], "internal: gradient_penalty needs conv4's activation materialised");
   hipLaunchKernelGGL(fill_f32_kernel, dim3(1), dim3(256), 0, st, ones, n, 1.0f);
   GI_LAUNCH_CHECK();
   GI_TRY(patchgan_backward(net, s, ones, gimg, 0));
-  // 2) penalty value and v = d(penalty)/dg
-  GI_TRY(op_gp_direction(st, gimg, n, (int64_t)H * W, lam, sumsq, vimg, penalty_out));
+  // 2) penalty value and the scaled direction v * s = s * d(penalty)/dg
+  GI_TRY(op_gp_direction(st, gimg, n, (int64_t)H * W, lam, sumsq, amax, vimg, penalty_out, sc));
+  // the parameter gradients of steps 3-4 go to the private buffer (gi_net::oGPgrad), added to the bound ones times 1/s at the end
+  float* const grads = net->grads;
+  float* const gbuf = (float*)net->shared(net->oGPgrad);
+  GI_HIP(hipMemsetAsync(gbuf, 0, (size_t)net->n_params * 4, st));
+  struct GradsBack { gi_net* net; float* g; ~GradsBack() { net->grads = g; } } grads_back{net, grads};
+  net->grads = gbuf;
   // 3) tangent forward
   void* TZ = net->shared(net->oTZ);
   {
@@ -1789,11 +1806,13 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
   h.a4 = A2(4, 0); h.w5 = net->params + net->w5_off; h.wl = net->params + net->wl_off; h.bl = net->params + net->bl_off;
   h.h = th; h.out = ytmp; h.n = n; h.Hh = net->Hh; h.Wh = net->Wh; h.c = 512; h.sigmoid = 0;
   GI_TRY(op_head_forward(st, dt, h));
-  // 4) reverse pass over the tangent graph (seed d(phi)/d(tz) = 1; the Linear bias does not enter phi)
+  // 4) reverse pass over the tangent graph (seed d(phi)/d(tz) = L; the Linear bias does not enter phi). dw5 / dwl: the head
+  // kernels form them from the unscaled seed and the tangent ta4 / h (s), into fixed-order partials (no float atomics)
   HeadBwdArgs hb;
   hb.a4 = A2(4, 0); hb.w5 = h.w5; hb.wl = h.wl; hb.h = th; hb.out = ytmp; hb.dy = ones; hb.da4 = G2(4, 0);
   hb.dw5 = net->grads + net->w5_off; hb.dwl = net->grads + net->wl_off; hb.dbl = nullptr; hb.dh = dth;
-  hb.n = n; hb.Hh = net->Hh; hb.Wh = net->Wh; hb.c = 512; hb.sigmoid = 0; hb.loss_scale = 1.f;
+  hb.n = n; hb.Hh = net->Hh; hb.Wh = net->Wh; hb.c = 512; hb.sigmoid = 0; hb.loss_scale = LS;
+  hb.scratch = (float*)net->shared(net->oHw); hb.scratch_bytes = net->hw_bytes;
   GI_TRY(op_head_backward(st, dt, hb));
   GI_HIP(hipMemsetAsync(G2(4, 1), 0, (size_t)n * net->Hh * net->Wh * 512 * T, st));   // no primal gradient enters above the head
   char* D2 = net->shared(net->oD2);
@@ -1804,15 +1823,15 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
     // tangent-gradient chain: d(tx_i) = J_BN( slope * d(ta_i) )
     GI_TRY(act_bn_bwd(net, s, G2(i, 0), c.ca, 0, nullptr, 0, 0, net->slot(s, net->oA[i]), c.ca, 0, net->slot(s, net->oRd[i]), D2, pix, c.ca,
                       GI_ACT_LRELU, 1.f, &net->dbn[i], 0));
-    // primal chain: standard BatchNorm backward of the gradient arriving from the layer above
+    // primal chain: standard BatchNorm backward of the gradient arriving from the layer above (dgamma / dbeta: s * L, 1/L removed)
     GI_TRY(act_bn_bwd(net, s, G2(i, 1), c.ca, 0, nullptr, 0, 0, net->slot(s, net->oA[i]), c.ca, 0, net->slot(s, net->oRd[i]), D2 + half, pix,
                       c.ca, GI_ACT_LRELU, 1.f, &net->dbn[i], 1));
-    // dependence of the BatchNorm Jacobian on the primal input
+    // dependence of the BatchNorm Jacobian on the primal input (dgamma: s * L, 1/L removed here)
     BNPtrs bp = bn_ptrs(net, s, net->dbn[i]);
     GI_TRY(op_bn_tangent_inject(st, dt, G2(i, 0), net->slot(s, net->oA[i]), net->shared(net->oTX[i]), net->slot(s, net->oRd[i]), D2 + half, pix,
-                                c.ca, net->params + net->dbn[i].gamma_off, bp.mean, bp.inv, net->grads + net->dbn[i].gamma_off,
+                                c.ca, net->params + net->dbn[i].gamma_off, bp.mean, bp.inv, net->grads + net->dbn[i].gamma_off, iLS,
                                 (float*)net->shared(net->oGPpart), (float*)net->shared(net->oGPsums)));
-    // conv_i on the stacked 2n batch: [d(tx_i); dxp_i] x [ta_{i-1}; a_{i-1}]
+    // conv_i on the stacked 2n batch: [d(tx_i); dxp_i] x [ta_{i-1}; a_{i-1}] (both products s * L; wgrad removes L)
     GI_TRY(wgrad(net, D2, c.ca, c.ca, 0, 0, A2(i - 1, 0), c.cb, c.cb, 0, 2 * n, Hs, Ws, net->grads + c.w_off));
     GI_TRY(igemm(net, 1, D2, c.ca, c.ca, 0, phase_ptr(net, c), G2(i - 1, 0), c.cb, c.cb, 0, 2 * n, Hs, Ws, 0, GI_ACT_NONE, false, nullptr));
   }
@@ -1821,10 +1840,13 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
     GI_TRY(act_bn_bwd(net, s, G2(1, 0), 64, 0, nullptr, 0, 0, net->slot(s, net->oA[1]), 64, 0, nullptr, D2, pix, 64, GI_ACT_LRELU, 1.f, nullptr, 0));
     GI_TRY(act_bn_bwd(net, s, G2(1, 1), 64, 0, nullptr, 0, 0, net->slot(s, net->oA[1]), 64, 0, nullptr, D2 + half, pix, 64, GI_ACT_LRELU, 1.f,
                       nullptr, 0));
-    GI_TRY(op_c1_wgrad(st, dt, D2, vimg, net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0, 1.f, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
+    // conv1: tangent half against v * s (L * s), primal half against xhat (s * L)
+    GI_TRY(op_c1_wgrad(st, dt, D2, vimg, net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0, iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
     GI_TRY(op_c1_wgrad(st, dt, D2 + half, (const float*)net->slot(s, net->oX), net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0,
-                       1.f, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
+                       iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
   }
+  // 5) bound gradients += private buffer * 1/s
+  GI_TRY(op_gp_unscale_add(st, gbuf, sc, grads, net->n_params));
   return GI_OK;
 }
 
@@ -1834,11 +1856,14 @@ extern "C" int gi_patchgan_gradient_penalty(gi_net* net, const float* xhat, int 
   GI_REQUIRE(net && net->bound && net->kind == 1, "gradient_penalty: bound discriminator handle required");
   GI_REQUIRE(xhat && n >= 1 && n <= net->max_n, "gradient_penalty: n=%d (max %d)", n, net->max_n);
   // the interpolates are ONE BatchNorm population whatever the stacked real|fake passes around this call use
-  // (gi_net_set_bn_groups): the penalty's primal forward, its backward and the tangent passes all run with one group
-  const int groups = net->bn_groups;
+  // (gi_net_set_bn_groups): the penalty's primal forward, its backward and the tangent passes all run with one group.
+  // The tangent passes read conv4's activation: the penalty's primal forward materialises it (no fp16 head fusion there).
+  const int groups = net->bn_groups, fuse_head = net->fuse_head;
   net->bn_groups = 1;
+  net->fuse_head = 0;
   const int rc = patchgan_gradient_penalty(net, xhat, n, lam, penalty_out);
   net->bn_groups = groups;
+  net->fuse_head = fuse_head;
   return rc;
 }
 
@@ -1896,9 +1921,10 @@ extern "C" int gi_net_debug_nonzero_tickets(gi_net* net, int* count) {
   return GI_OK;
 }
 
-extern "C" int gi_net_saved_activation(gi_net* net, int slot, int kind, int level, float* out_nchw, int64_t count) {
-  GI_REQUIRE(net && net->bound && out_nchw, "saved_activation: net not bound / null output");
-  GI_REQUIRE(slot >= 0 && slot < net->n_slots && net->slot_n[slot] > 0, "saved_activation: slot %d holds no forward", slot);
+namespace {
+// slot: a user slot, or a critic's gp_slot (gi_patchgan_gp_saved_activation)
+int saved_activation(gi_net* net, int slot, int kind, int level, float* out_nchw, int64_t count) {
+  GI_REQUIRE(net->slot_n[slot] > 0, "saved_activation: slot %d holds no forward", slot);
   GI_REQUIRE(!(net->kind == 0 && net->slot_inference[slot]), "saved_activation: slot %d holds an inference forward (nothing saved)", slot);
   const int n = net->slot_n[slot];
   const void* src = nullptr;
@@ -1938,6 +1964,19 @@ extern "C" int gi_net_saved_activation(gi_net* net, int slot, int kind, int leve
                        act, npg, gstride);
   GI_LAUNCH_CHECK();
   return GI_OK;
+}
+}  // namespace
+
+extern "C" int gi_net_saved_activation(gi_net* net, int slot, int kind, int level, float* out_nchw, int64_t count) {
+  GI_REQUIRE(net && net->bound && out_nchw, "saved_activation: net not bound / null output");
+  GI_REQUIRE(slot >= 0 && slot < net->n_slots && net->slot_n[slot] > 0, "saved_activation: slot %d holds no forward", slot);
+  return saved_activation(net, slot, kind, level, out_nchw, count);
+}
+
+extern "C" int gi_patchgan_gp_saved_activation(gi_net* net, int level, float* out_nchw, int64_t count) {
+  GI_REQUIRE(net && net->bound && net->kind == 1 && out_nchw, "gp_saved_activation: bound discriminator handle / output required");
+  GI_REQUIRE(net->slot_n[net->gp_slot] > 0, "gp_saved_activation: no gradient penalty has run on this handle");
+  return saved_activation(net, net->gp_slot, 0, level, out_nchw, count);
 }
 
 // weight gradients on the second stream (side_begin), joined before the caller sees the gradients

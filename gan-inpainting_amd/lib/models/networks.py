@@ -701,7 +701,9 @@ class PatchGANDiscriminator(HipNet):
         """WGAN-GP extension (not in the reference): adds d/dtheta of
         lam * mean_n (||grad_x D(xhat)_n||_2 - 1)^2, xhat = eps*real + (1-eps)*fake, to the parameter
         gradients and returns the penalty (0-d device tensor). eps: (n,) in [0,1), drawn here if None.
-        fp32 critics built with sigmoid=False."""
+        Critics built with sigmoid=False, fp16 or fp32. fp16: the tangent pass runs at a power-of-two scale the
+        library derives on the device per call (gi_patchgan_gradient_penalty), the reverse passes at the network's loss
+        scale; an overflow leaves inf / NaN in the gradients for the optimizers' overflow guard."""
         real, fake = real.contiguous(), fake.detach().contiguous()
         n, _, H, W = real.shape
         if eps is None:
@@ -720,6 +722,13 @@ class PatchGANDiscriminator(HipNet):
         B.check(lib.gi_patchgan_gradient_penalty(self._handle, B.ptr(xhat), n, float(lam), B.ptr(out)))
         self._nbt_pending += 1   # the penalty's own forward runs the BatchNorm layers in train mode
         return out.view(())
+
+    def gp_saved_activation(self, level, shape):
+        """saved_activation(0, level, shape) of the last gradient_penalty's own primal forward (its private activation set,
+        gi_patchgan_gp_saved_activation): the kink decisions that forward took. Parity tests only."""
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+        B.check(B.lib().gi_patchgan_gp_saved_activation(self._handle, level, B.ptr(out), out.numel()))
+        return out
 
 
 class VGG19Wrapper(nn.Module):

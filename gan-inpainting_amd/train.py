@@ -72,7 +72,7 @@ def main(argv=None):
     # backend additions
     parser.add_argument("--dtype", choices=["fp16", "fp32"], default="fp16")
     parser.add_argument("--gp-lambda", dest="gp_lambda", type=float, default=0.0,
-                        help="> 0: WGAN-GP gradient penalty (extension, fp32) instead of the reference's weight clipping")
+                        help="> 0: WGAN-GP gradient penalty (extension) instead of the reference's weight clipping")
     parser.add_argument("--face-parsing", dest="face_parsing", choices=["off", "random"], default="off",
                         help="random: a randomly initialised frozen UnetGenerator(1,4,7,ngf=32) stands in for the reference's "
                              "_states/face_segmentation checkpoint (train.py:169-175), which is not available")

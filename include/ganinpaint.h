@@ -206,8 +206,15 @@ int gi_allreduce_wait(gi_comm* comm, void* hip_comm_stream, void* hip_compute_st
 /* WGAN-GP EXTENSION (not in the reference, which clips weights: wgan_l1.py:151-153): accumulates the
  * parameter gradient of  lam * mean_n (||grad_x D(xhat)_n||_2 - 1)^2  into the bound grads and writes the
  * penalty to penalty_out[0] (device). xhat: (n,1,H,W) interpolates, e.g. from gi_interpolate.
- * fp32 critics without sigmoid, train mode. Uses a private activation set (no user slot is touched). */
+ * fp16 or fp32 critics without sigmoid, train mode. Uses a private activation set (no user slot is touched).
+ * Scaling: the tangent (Jacobian-vector) pass runs on v * s, v = d(penalty)/d(grad_x D), with ONE power of two
+ * s = 2^k per call derived on the device so that max|v * s| lies in [1, 2) (s = 1 when v is zero, e.g. lam = 0);
+ * the reverse passes are seeded with the network's loss scale (gi_net_set_loss_scale). Both are removed before the
+ * gradients are added to the bound ones; an overflow leaves inf / NaN there for the fp16 overflow guard. No sync. */
 int gi_patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, float* penalty_out);
+/* The activations of the last gi_patchgan_gradient_penalty's own primal forward (its private activation set), as
+ * gi_net_saved_activation of a critic with kind 0: level 1..4, fp32 (N,C,h,w), count = N*C*h*w. Parity tests only. */
+int gi_patchgan_gp_saved_activation(gi_net* net, int level, float* out_nchw, int64_t count);
 /* out[n] = eps[n]*real[n] + (1-eps[n])*fake[n] */
 int gi_interpolate(gi_ctx* ctx, const float* real, const float* fake, const float* eps, int n, int64_t hw, float* out);
 
