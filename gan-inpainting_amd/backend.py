@@ -31,6 +31,8 @@ PROTOTYPES = {
     "gi_unet_create_norm": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "gi_unet_create_padded": (_i, [_vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "gi_patchgan_create": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "gi_dcgan_create": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "gi_dcgan_debug_forward_convs": (_i, [_vp, _i, _vp, _i]),
     "gi_net_destroy": (_i, [_vp]),
     "gi_net_tensor_count": (_i, [_vp]),
     "gi_net_tensor_desc": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i),

@@ -1,6 +1,7 @@
 // Host-side schedules: which kernels run, in which order, on which buffers, for
 //   UnetGenerator      (lib/models/networks.py:216-324)  forward + backward
 //   PatchGANDiscriminator (networks.py:331-363)          forward + backward
+// (DCGANDiscriminator, networks.py:162-212, keeps its own state and schedule in dcgan.hip behind gi_net::dc)
 // Data layout in HBM (per activation slot): NHWC tensors of the compute type T; for every U-Net
 // level k one "concat buffer" C[k] = [skip a_k | decoder u_{k+1}] (2*ch_k channels) that both
 // producers write at their channel offset, so torch.cat (networks.py:324) never materialises.
@@ -67,9 +68,20 @@ struct Arena {
 
 }  // namespace
 
+// DCGANDiscriminator (dcgan.hip): the generic gi_net_* entries below hand a kind-2 handle to these
+struct gi_dcgan;
+void gi_dcgan_free(gi_dcgan* dc);
+int gi_dcgan_sync(gi_dcgan* dc, hipStream_t st, const float* params, char* ws);
+int gi_dcgan_forward(gi_dcgan* dc, hipStream_t st, const float* params, char* ws, int slot, const float* x, float* y, int n);
+int gi_dcgan_backward(gi_dcgan* dc, hipStream_t st, const float* params, float* grads, char* ws, int slot, const float* dy, float* dx,
+                      int need_wgrad, float loss_scale, int phase);
+int64_t gi_dcgan_phase_split(gi_dcgan* dc);
+int gi_dcgan_saved(gi_dcgan* dc, hipStream_t st, char* ws, int slot, int kind, int level, float* out, int64_t count);
+
 struct gi_net {
   gi_ctx* ctx = nullptr;
-  int kind = 0;  // 0 unet, 1 patchgan
+  int kind = 0;  // 0 unet, 1 patchgan, 2 dcgan (state in dc)
+  gi_dcgan* dc = nullptr;
   int dtype = GI_F32;
   int H = 0, W = 0, max_n = 0, n_slots = 1;
   int train = 1;
@@ -504,8 +516,34 @@ extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int ma
   return GI_OK;
 }
 
+// a kind-2 handle for gi_dcgan_create (dcgan.hip): inventory entries through gi_net_add_param, workspace size from dcgan.hip
+gi_net* gi_net_new_dcgan(gi_ctx* ctx, int dtype, int max_n, int n_slots, gi_dcgan* dc) {
+  gi_net* net = new gi_net();
+  net->ctx = ctx; net->kind = 2; net->dc = dc; net->dtype = dtype; net->H = 128; net->W = 128; net->max_n = max_n;
+  net->n_slots = n_slots;
+  net->loss_scale = dtype == GI_F16 ? 65536.f : 1.f;
+  return net;
+}
+void gi_net_add_param(gi_net* net, const char* name, int kind, const int64_t* shape, int ndim, int64_t* off) {
+  TensorDesc t;
+  t.name = name; t.kind = kind; t.ndim = ndim; t.numel = 1;
+  for (int i = 0; i < 4; ++i) { t.shape[i] = i < ndim ? shape[i] : 1; t.numel *= t.shape[i]; }
+  t.offset = net->n_params;
+  net->n_params += gi_align_up(t.numel, 64);
+  *off = t.offset;
+  net->tensors.push_back(t);
+}
+void gi_net_set_workspace(gi_net* net, int64_t bytes) { net->arena.size = bytes; }
+gi_dcgan* gi_net_dcgan_state(gi_net* net) { return net && net->kind == 2 ? net->dc : nullptr; }
+void gi_net_dcgan_bound(gi_net* net, hipStream_t* st, const float** params, char** ws) {
+  *st = net->bound ? net->ctx->stream : nullptr;
+  *params = net->params;
+  *ws = net->bound ? net->ws : nullptr;
+}
+
 extern "C" int gi_net_destroy(gi_net* net) {
   if (net) {
+    if (net->dc) gi_dcgan_free(net->dc);
     if (net->st2) { (void)hipStreamSynchronize(net->st2); (void)hipStreamDestroy(net->st2); }
     if (net->ev_dz) (void)hipEventDestroy(net->ev_dz);
     for (hipEvent_t e : net->ev_wg) if (e) (void)hipEventDestroy(e);
@@ -571,6 +609,7 @@ __global__ void __launch_bounds__(256) pad_b_kernel(const float* __restrict__ sr
 
 extern "C" int gi_net_sync_weights(gi_net* net) {
   GI_REQUIRE(net && net->bound, "sync_weights: net not bound");
+  if (net->kind == 2) return gi_dcgan_sync(net->dc, net->ctx->stream, net->params, net->ws);
   ++net->affine_gen;   // parameters (and possibly running statistics) were written from outside
   PackJobs P;
   P.n = 0;
@@ -614,8 +653,9 @@ extern "C" int gi_net_set_inference(gi_net* net, int inference) {
   return GI_OK;
 }
 extern "C" int gi_net_set_bn_groups(gi_net* net, int groups) {
-  GI_REQUIRE(net && net->kind == 1, "set_bn_groups: discriminator handle required");
+  GI_REQUIRE(net && net->kind != 0, "set_bn_groups: discriminator handle required");
   GI_REQUIRE(groups == 1 || groups == 2, "set_bn_groups: groups=%d (1 or 2)", groups);
+  if (net->kind == 2) return GI_OK;   // DCGAN: no BatchNorm, a stacked batch is plain rows
   net->bn_groups = groups;
   return GI_OK;
 }
@@ -1878,6 +1918,7 @@ extern "C" int gi_net_forward(gi_net* net, int slot, const float* x, float* y, i
   GI_REQUIRE(net && net->bound, "net_forward: net not bound");
   GI_REQUIRE(x && y && n >= 1 && n <= net->max_n, "net_forward: n=%d (max %d)", n, net->max_n);
   GI_REQUIRE(slot >= 0 && slot < net->n_slots, "net_forward: slot=%d", slot);
+  if (net->kind == 2) return gi_dcgan_forward(net->dc, net->ctx->stream, net->params, net->ws, slot, x, y, n);
   return net->kind == 0 ? unet_forward(net, slot, x, y, n) : patchgan_forward(net, slot, x, y, n);
 }
 
@@ -1969,6 +2010,10 @@ int saved_activation(gi_net* net, int slot, int kind, int level, float* out_nchw
 
 extern "C" int gi_net_saved_activation(gi_net* net, int slot, int kind, int level, float* out_nchw, int64_t count) {
   GI_REQUIRE(net && net->bound && out_nchw, "saved_activation: net not bound / null output");
+  if (net->kind == 2) {
+    GI_REQUIRE(slot >= 0 && slot < net->n_slots, "saved_activation: slot=%d", slot);
+    return gi_dcgan_saved(net->dc, net->ctx->stream, net->ws, slot, kind, level, out_nchw, count);
+  }
   GI_REQUIRE(slot >= 0 && slot < net->n_slots && net->slot_n[slot] > 0, "saved_activation: slot %d holds no forward", slot);
   return saved_activation(net, slot, kind, level, out_nchw, count);
 }
@@ -1981,6 +2026,8 @@ extern "C" int gi_patchgan_gp_saved_activation(gi_net* net, int level, float* ou
 
 // weight gradients on the second stream (side_begin), joined before the caller sees the gradients
 static int backward_joined(gi_net* net, int slot, const float* dy, float* dx, int need_wgrad, int phase) {
+  if (net->kind == 2)
+    return gi_dcgan_backward(net->dc, net->ctx->stream, net->params, net->grads, net->ws, slot, dy, dx, need_wgrad, net->loss_scale, phase);
   GI_TRY(side_begin(net, need_wgrad));
   const int rc = net->kind == 0 ? unet_backward(net, slot, dy, dx, need_wgrad, phase) : patchgan_backward(net, slot, dy, dx, need_wgrad, phase);
   const int rj = side_join(net);
@@ -2007,6 +2054,7 @@ extern "C" int gi_net_backward_phase(gi_net* net, int slot, const float* dy, flo
 // the conv4 weight)
 extern "C" int64_t gi_net_phase_split(gi_net* net) {
   if (!net) return GI_ERR_INVALID;
+  if (net->kind == 2) return gi_dcgan_phase_split(net->dc);
   if (net->kind != 0) return net->dconv[4].w_off;
   return net->up[net->nd].w_off;
 }

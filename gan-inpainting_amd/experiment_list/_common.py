@@ -52,16 +52,30 @@ def setup(state, title):
 
 
 def build_networks(state, device, n_disc=1, sigmoid=True):
+    """The generator and n_disc discriminators of a plugin. -d chooses the discriminator of the minimax plugins
+    (minimaxgan_*, experiment1_global_local_D: PatchGAN or DCGAN); the WGAN plugins (sigmoid=False) always build a
+    PatchGAN critic, as the reference hard-codes it (wgan_l1.py:58)."""
     size = state["imagedim"]
     dtype = state.get("dtype", "fp16")
-    if state.get("generator", "unet") != "unet" or state.get("discriminator", "patchgan") != "patchgan":
-        raise NotImplementedError("HIP backend accelerates -g unet -d patchgan (the reference defaults, train.py:27-28)")
+    disc = state.get("discriminator", "patchgan")
+    if state.get("generator", "unet") != "unet" or disc not in ("patchgan", "dcgan"):
+        raise NotImplementedError("HIP backend accelerates -g unet with -d patchgan or -d dcgan (train.py:27-28)")
+    if disc == "dcgan" and not sigmoid:
+        logging.getLogger(state.get("title", __name__)).info(
+            "-d dcgan ignored: this plugin builds a PatchGAN critic without sigmoid, as the reference does (wgan_l1.py:58)")
+        disc = "patchgan"
+    if disc == "dcgan" and size != 128:
+        raise ValueError(f"-d dcgan needs --imagedim 128: DCGANDiscriminator's Linear(36864, 4096) reads the 1024 x 6 x 6 "
+                         f"features of a 128x128 image, got --imagedim {size}")
     num_downs = state.get("num_downs", 7 if size >= 128 else 6)
     if num_downs == 7:
         G = networks.get_network("generator", "unet", dtype=dtype)
     else:
         G = networks.UnetGenerator(1, 1, num_downs, ngf=64, use_dropout="False", dtype=dtype)
-    Ds = [networks.PatchGANDiscriminator(sigmoid=sigmoid, image_size=size, dtype=dtype).to(device) for _ in range(n_disc)]
+    if disc == "dcgan":   # experiment1_global_local_D: global and local discriminator both (reference :115-116)
+        Ds = [networks.DCGANDiscriminator(dtype=dtype).to(device) for _ in range(n_disc)]
+    else:
+        Ds = [networks.PatchGANDiscriminator(sigmoid=sigmoid, image_size=size, dtype=dtype).to(device) for _ in range(n_disc)]
     return G.to(device), Ds
 
 

@@ -1,5 +1,5 @@
-"""Drop-in for the reference's lib/models/networks.py (get_network :13-28, UnetGenerator :216-253,
-PatchGANDiscriminator :331-363) on the HIP backend.
+"""Drop-in for the reference's lib/models/networks.py (get_network :13-28, DCGANDiscriminator :162-212,
+UnetGenerator :216-253, PatchGANDiscriminator :331-363) on the HIP backend.
 
 The classes are torch.nn.Modules whose parameters/buffers are zero-copy views into flat fp32
 device buffers owned by the module and bound to a libganinpaint handle:
@@ -47,7 +47,7 @@ def get_norm_layer(norm_type="instance"):
 
 
 def get_network(type, name, **kw):
-    """networks.py:13-28. vgg19 / dcgan are not on the accelerated path."""
+    """networks.py:13-28. vgg19 is not on the accelerated path."""
     if type == "generator":
         if name == "unet":
             return UnetGenerator(1, 1, 7, ngf=64, norm_layer=get_norm_layer(norm_type="batch"),
@@ -59,7 +59,7 @@ def get_network(type, name, **kw):
         if name == "patchgan":
             return PatchGANDiscriminator(**kw)
         if name == "dcgan":
-            raise NotImplementedError("DCGANDiscriminator is outside the HIP backend's hot path")
+            return DCGANDiscriminator(**kw)
         raise Exception("Invalid discriminator network name")
     raise Exception("Invalid network type")
 
@@ -90,6 +90,7 @@ class HipNet(nn.Module):
     """Common machinery: inventory, flat buffers, handle (re)creation, raw forward/backward."""
 
     n_slots = 3
+    _rows_per_image = 1          # output rows per input image (DCGANDiscriminator: 2, one per softmax probability)
 
     def __init__(self, dtype=None):
         super().__init__()
@@ -335,7 +336,7 @@ class HipNet(nn.Module):
             raise B.BackendError(f"activations of this forward were overwritten: more than {self.n_slots} forwards of "
                                  f"{type(self).__name__} were live before their backward")
         dy = dy.contiguous().float()
-        n = dy.shape[0]
+        n = dy.shape[0] // self._rows_per_image
         dx = torch.empty((n, 1, self._geom[0], self._geom[1]), dtype=torch.float32, device=dy.device) if need_dx else None
         self._attach_grads()
         if self._slot_groups[slot] != self._groups_set:
@@ -729,6 +730,67 @@ class PatchGANDiscriminator(HipNet):
         out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
         B.check(B.lib().gi_patchgan_gp_saved_activation(self._handle, level, B.ptr(out), out.numel()))
         return out
+
+
+class DCGANDiscriminator(HipNet):
+    """networks.py:162-212: 4 x [Conv2d 5x5 s1 p1 + bias, ReLU, MaxPool 2/2] (1 -> 128 -> 256 -> 512 -> 1024 channels),
+    Linear(36864, 4096), ReLU, Linear(4096, 512), ReLU, Linear(512, 2), Softmax over the two logits; returns the
+    probabilities as x.view(-1, 1), i.e. (2N, 1) with row 2i + j = p_j of image i. Linear 12 flattens the last pooled map in
+    NCHW order, so only 128x128 images fit it (1024 * 6 * 6 = 36864). No BatchNorm, no dropout: train and eval forwards
+    are the same. Conv weights are logical [out, in, 5, 5] views with channels_last strides."""
+
+    def __init__(self, dtype=None):
+        super().__init__(dtype)
+        lib = B.lib()
+        h = C.c_void_p()
+        B.check(lib.gi_dcgan_create(None, 128, 128, 1, self._dtype, 1, C.byref(h)))
+        self._build_tree(self._inventory(h), lib.gi_net_param_floats(h), lib.gi_net_buffer_floats(h))
+        lib.gi_net_destroy(h)
+        self.reset_parameters()
+
+    @staticmethod
+    def _view(flat, t):
+        v = flat[t["offset"]: t["offset"] + t["numel"]]
+        if t["kind"] == 0:  # physical [a][ky][kx][b] -> logical [a,b,5,5] (channels_last strides)
+            a, b, kh, kw = t["shape"]
+            return v.view(a, kh, kw, b).permute(0, 3, 1, 2)
+        return v.view(*t["shape"])
+
+    def reset_parameters(self):
+        """torch's RNG consumed as the reference constructor does: module order, default Conv2d / Linear init."""
+        with torch.no_grad():
+            chans = [1, 128, 256, 512, 1024]
+            for i in range(4):
+                m = nn.Conv2d(chans[i], chans[i + 1], (5, 5), (1, 1), padding=(1, 1))
+                self._tensor(f"model.{3 * i}.weight").copy_(m.weight.detach())
+                self._tensor(f"model.{3 * i}.bias").copy_(m.bias.detach())
+            for idx, (fi, fo) in zip((12, 14, 16), ((36864, 4096), (4096, 512), (512, 2))):
+                m = nn.Linear(fi, fo, bias=True)
+                self._tensor(f"model.{idx}.weight").copy_(m.weight.detach())
+                self._tensor(f"model.{idx}.bias").copy_(m.bias.detach())
+        self._dirty = True
+
+    _rows_per_image = 2
+
+    @staticmethod
+    def _check_size(H, W):
+        if (H, W) != (128, 128):
+            raise ValueError(f"DCGANDiscriminator takes 128x128 images: its Linear(36864, 4096) reads the 1024 x 6 x 6 = 36864 "
+                             f"features of a 128x128 input, got {(H, W)}")
+
+    def _create_handle(self, ctx, H, W, max_n):
+        self._check_size(H, W)
+        h = C.c_void_p()
+        B.check(B.lib().gi_dcgan_create(ctx, H, W, max_n, self._dtype, self.n_slots, C.byref(h)))
+        return h
+
+    def _output_shape(self, n, H, W):
+        return (self._rows_per_image * n, 1)
+
+    def _forward_raw(self, x, bn_groups=1, inference=False):
+        if x.dim() == 4:
+            self._check_size(x.shape[2], x.shape[3])   # before the device checks: the size error is the same everywhere
+        return super()._forward_raw(x, bn_groups, inference)
 
 
 class VGG19Wrapper(nn.Module):

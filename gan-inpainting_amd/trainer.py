@@ -118,8 +118,9 @@ class _StepBase:
             mk = lambda: torch.empty_like(ground)  # noqa: E731
             self.mask_c, self.masked, self.inpainted = mk(), mk(), mk()
             self.g_adv, self.g_rec, self.g_gen, self.tmp1, self.tmp2 = mk(), mk(), mk(), mk(), mk()
-            n = ground.shape[0]
-            self.dpred = torch.empty((n, 1), dtype=torch.float32, device=ground.device)
+            n, _, h, w = ground.shape
+            # prediction / its gradient as the discriminator returns it: (n, 1), or (2n, 1) for DCGANDiscriminator
+            self.dpred = torch.empty(self.Ds[0]._output_shape(n, h, w), dtype=torch.float32, device=ground.device)
             self.L = {}
             if self.auto_loss_scale:
                 self._pick_loss_scales(ground)
@@ -215,7 +216,7 @@ class _StepBase:
         key = (id(net), tuple(real.shape))
         if key not in bufs:
             bufs[key] = (torch.empty((2 * n,) + tuple(real.shape[1:]), dtype=torch.float32, device=real.device),
-                         torch.empty((2 * n, 1), dtype=torch.float32, device=real.device))
+                         torch.empty(net._output_shape(2 * n, real.shape[2], real.shape[3]), dtype=torch.float32, device=real.device))
         own, dp2 = bufs[key]
         if x2 is None:
             x2 = own
@@ -224,7 +225,7 @@ class _StepBase:
         if fake.data_ptr() != x2[n:].data_ptr():      # the caller may have produced `fake` in the pair buffer already
             x2[n:].copy_(fake)
         p, t = self._fwd(net, x2, bn_groups=2)
-        o.adv_pair(p, n, kind, t_real, t_fake, self._loss(name_real), self._loss(name_fake), dp2, gs_real, gs_fake)
+        o.adv_pair(p, p.shape[0] // 2, kind, t_real, t_fake, self._loss(name_real), self._loss(name_fake), dp2, gs_real, gs_fake)
         if synced:
             self._bwd_D_synced(net, t, dp2)
         else:

@@ -126,6 +126,22 @@ int gi_unet_create_padded(gi_ctx* ctx, int num_downs, int ngf, int ch1, int out_
 /* PatchGANDiscriminator(c=1, sigmoid): Linear(25,1) generalised to ((H/16-3)*(W/16-3),1). */
 int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int max_n, int dtype, int n_slots,
                        gi_net** out);
+/* DCGANDiscriminator() (reference lib/models/networks.py:162-212; get_network('discriminator', 'dcgan'), :23-24):
+ * 4 x [Conv2d 5x5 s1 p1 + bias, ReLU, MaxPool 2/2], Linear 36864 -> 4096 -> 512 -> 2 (ReLU between), Softmax over the
+ * two logits, view(-1, 1): y is (2n, 1), row 2i + j = p_j of image i. H = W = 128 only (Linear 12's 36864 = 1024*6*6
+ * inputs). Conv weights are kind 0 of shape [a,b,5,5] (physical [a][ky][kx][b]), the Linears kind 1; no buffers. The
+ * generic gi_net_* entries apply; gi_net_set_bn_groups is accepted and has no effect (no BatchNorm), set_train /
+ * set_inference change nothing (train and eval forwards are the same). Backward phases: 1 = softmax .. Linear 12 (range
+ * [gi_net_phase_split(), end)), 2 = the convolutions. gi_net_saved_activation kinds: 0 = pooled map of conv `level`
+ * (1..4, (n,C,h,w)); 1 = its pool decisions, sub-position (dy*2+dx) of the window's maximum + 4 if that pre-activation
+ * was > 0; 2 = level 1 ReLU(Linear 12) (n,4096), level 2 ReLU(Linear 14) (n,512), level 3 the probabilities (n,2).
+ * The convolutions' pre-activations are not kept: the forward stores only the pooled maps, and the decision byte already
+ * holds every choice the backward makes there (which window element wins and whether it passes the ReLU). A parity test
+ * measures the ambiguity bands on the reference's own pre-activations and imposes these decisions inside them. */
+int gi_dcgan_create(gi_ctx* ctx, int H, int W, int max_n, int dtype, int n_slots, gi_net** out);
+/* Debug (tests: which kernel serves the convolution forward): the four convolution blocks of a forward of n images into
+ * `slot`, nothing after them; the slot then holds no forward that a backward could use. */
+int gi_dcgan_debug_forward_convs(gi_net* net, int slot, const float* x, int n);
 int gi_net_destroy(gi_net* net);
 
 /* parameter / buffer inventory, in the reference's named_parameters() order, then buffers.
