@@ -96,6 +96,19 @@ PROTOTYPES = {
     "gi_vgg19_sync_weights": (_i, [_vp]),
     "gi_vgg19_perceptual_style": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp]),
     "gi_vgg19_features": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gi_inception_create": (_i, [_vp, _i, _i, _vp]),
+    "gi_inception_destroy": (None, [_vp]),
+    "gi_inception_param_floats": (_i64, [_vp]),
+    "gi_inception_workspace_bytes": (_i64, [_vp]),
+    "gi_inception_num_tensors": (_i, [_vp]),
+    "gi_inception_tensor_desc": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "gi_inception_bind": (_i, [_vp, _vp, _vp, _i64]),
+    "gi_inception_sync_weights": (_i, [_vp]),
+    "gi_inception_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "gi_inception_debug_forward_convs": (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    "gi_fid_stats_acc_doubles": (_i64, [_i]),
+    "gi_fid_stats_update": (_i, [_vp, _vp, _vp, _i, _i]),
+    "gi_fid_stats_finish": (_i, [_vp, _vp, _vp, _vp, _i]),
     "gi_resize_output_size": (_i, [_i, _i, _i, _vp, _vp]),
     "gi_resize_table_bytes": (_i64, [_i, _i, _i, _i]),
     "gi_resize_build_tables": (_i, [_vp, _i, _i, _i, _i, _vp]),

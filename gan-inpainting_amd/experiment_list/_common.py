@@ -9,8 +9,8 @@ Differences to the reference, all host-side and listed in DESIGN.md:
   * the gradient-flow histogram (one .item() per tensor per batch, :180-182,:195-197) is one kernel +
     one copy per batch (util.GradFlow), accumulated on the device;
   * the evaluation pass (minimaxgan_l1.py:234-240) runs lib.models.evaluate.calculate_metric on the
-    train and test loaders (reconstruction metrics on fused HIP reductions; FID reported as -1, needs
-    Inception weights); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch).
+    train and test loaders (reconstruction metrics on fused HIP reductions; FID when state['inception_model']
+    and state['train_fid'] / state['test_fid'] are set (train.py --fid-weights), else -1); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch).
 """
 import contextlib
 import logging
@@ -92,6 +92,12 @@ def to_device_images(t, device, state):
     return t.float().contiguous()
 
 
+def _fid_stats(state, mode):
+    """state["train_fid"] / state["test_fid"] (train.py:177-178), or the reference's "not computed" pair."""
+    st = state.get(mode + "_fid")
+    return (-1, -1) if st is None or isinstance(st, (int, float)) else st
+
+
 def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn, d_names, pass_extra=False, step=None):
     """batch_fn(batch_index, ground, mask[, extra]) -> (loss dict of device scalars, g_updated: bool); extra = the
     loader's third item (the segmentation labels of dataset.py:35-51) when pass_extra is set."""
@@ -155,7 +161,8 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                 eval_hist.append(state["eval_fn"](net_G, loaders.get("test"), epoch))
             else:                                                # minimaxgan_l1.py:235-240
                 prep = lambda t: to_device_images(t, device, state)   # noqa: E731
-                rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, mode=k, epoch=epoch, prepare=prep)
+                rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
+                                                         inception_model=state.get("inception_model"), epoch=epoch, prepare=prep)
                             for k in ("train", "test") if loaders.get(k) is not None}
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))

@@ -6,8 +6,12 @@
 The reference file does not import (mixed indentation, undefined `l1_criterion` / `segment`); what is
 mirrored is what its plugins rely on (minimaxgan_l1.py:236-237: a dict with recon_rmse_global,
 recon_l1_global, recon_rmse_local, recon_l1_local, fid, epoch). Out of this backend's scope and
-reported as such: FID (Inception weights; `fid` is -1, the reference's own "not computed" value, :150),
-the JPEG dump that feeds it (:145-148), the matplotlib panels (`from_model_object`, `from_saved_obj`).
+reported as such: the matplotlib panels (`from_model_object`, `from_saved_obj`). FID (:155-163) is opt-in:
+with `fid_stats` and an `inception_model` (lib.fid.inception.InceptionV3, weights loaded from a local file)
+the pass feeds the composites the reference saves per image to the Inception handle and the fp64 device
+statistic; without them `fid` is -1, the reference's own "not computed" value (:160). The reference writes
+the composites as JPEG files and reads them back; here they keep the 8-bit truncation of
+`(x * 255).astype(uint8)` but skip the file round trip (and with it JPEG's lossy coding).
 Like the reference, calculate_metric does NOT switch the network to eval(): BatchNorm and Dropout run
 in whatever mode the caller left them (training mode in the plugins)."""
 import ctypes as C
@@ -45,11 +49,17 @@ class ReconMeter:
 
 @torch.no_grad()
 def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", inception_model=None, epoch=None,
-                     is_flip_mask=False, prepare=None):
+                     is_flip_mask=False, prepare=None, fid_capture=None):
     """evaluate.py:85-177. `loader` yields (input, mask, _) like the reference's datasets; `prepare` (optional)
-    maps a loader item to a (n,1,h,w) float32 device tensor (the device Resize + ToTensor for decoded bytes)."""
+    maps a loader item to a (n,1,h,w) float32 device tensor (the device Resize + ToTensor for decoded bytes).
+    `fid_capture` (optional dict, tests): receives the composites fed to Inception and the pass's (mu, sigma)."""
     lib = B.lib()
     meter = ReconMeter(device)
+    fid_on = inception_model is not None and not _no_fid_stats(fid_stats)
+    stats = None
+    if fid_on:
+        from ..fid import fid_score
+        stats = fid_score.FidStats(inception_model.flat.device, 2048)
     for inp, mask, *_ in loader:
         if prepare is not None:
             inp, mask = prepare(inp), prepare(mask)
@@ -61,10 +71,31 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         B.check(lib.gi_mask_apply(B.get_ctx(inp.device), B.ptr(inp), B.ptr(mask), B.ptr(m), B.ptr(masked), inp.numel(),
                                   1 | (2 if is_flip_mask else 0)))                  # :128-133
         out = net(masked)                                                            # :134
-        meter.update(inp, out.detach().contiguous(), m)                              # :135-143
+        out = out.detach().contiguous()
+        meter.update(inp, out, m)                                                    # :135-143
+        if fid_on:
+            comp = torch.empty_like(out)                                             # :136 out * m + masked
+            B.check(lib.gi_mask_composite(B.get_ctx(out.device), B.ptr(masked), B.ptr(out), B.ptr(m), B.ptr(comp), out.numel()))
+            comp = fid_score.quantize8(comp)                                         # :155-158 without the file
+            stats.update(inception_model.features(comp))
+            if fid_capture is not None:
+                fid_capture.setdefault("composites", []).append(comp.cpu())
     metric = meter.result()
-    metric.update({"fid": -1, "epoch": epoch})                                       # :150 (FID out of scope)
+    fid = -1                                                                         # :160
+    if fid_on:
+        mu, sigma = stats.finish()
+        fid = fid_score.calculate_frechet_distance(fid_stats[0], fid_stats[1], mu, sigma)   # :161-163
+        if fid_capture is not None:
+            fid_capture.update(mu=mu, sigma=sigma)
+    metric.update({"fid": fid, "epoch": epoch})
     return metric
+
+
+def _no_fid_stats(fid_stats):
+    """The reference's `fid_stats[0] == -1 and fid_stats[1] == -1` (:161); None counts as not computed too."""
+    if fid_stats is None or isinstance(fid_stats, (int, float)):
+        return True
+    return all(s is None or (not hasattr(s, "shape") and s == -1) for s in (fid_stats[0], fid_stats[1]))
 
 
 def calculate_segmentation_eval_metric(labels, outputs, unique_labels):

@@ -5,8 +5,8 @@ on the HIP backend. The reference launcher does not run as written (SURVEY.md se
 variable names at :173,:180,:183 and a hard-coded dataset path :64); this one iterates over
 --experiments as evidently intended and takes the data as --data synthetic (the benchmark's masked-
 image batches) or --data <dir> in the reference's dataset layout (csv/train_all_masks.csv, csv/test_all_masks.csv listing image
-files; decoded on the host with PIL, resized + normalised on the device). FID statistics (train.py:157-166) are
-outside the backend's scope; the face-segmentation checkpoint (:169-175) is not available (--face-parsing random).
+files; decoded on the host with PIL, resized + normalised on the device). FID statistics (train.py:157-166) are computed on the device when
+--fid-weights names a local copy of the published Inception state dict (never downloaded); the face-segmentation checkpoint (:169-175) is not available (--face-parsing random).
 
     python gan-inpainting_amd/train.py -exp wgan_l1 -ep 2 -b 32 --imagedim 256 --data synthetic
     python -m torch.distributed.run --nproc-per-node 8 gan-inpainting_amd/train.py -exp wgan_rmse ...
@@ -81,6 +81,9 @@ def main(argv=None):
     parser.add_argument("--workers", type=int, default=0,
                         help="DataLoader worker processes (0 = decode in the training process like the reference, train.py:148-152; "
                              "the PNG decode, not the GPU, bounds real-data throughput at 0)")
+    parser.add_argument("--fid-weights", dest="fid_weights", default="",
+                        help="local path of the published FID Inception state dict (pt_inception-2015-12-05-*.pth); enables FID in the "
+                             "evaluation pass (train.py:154-180). Nothing is ever downloaded; without the flag fid stays -1")
     parser.add_argument("--data", default="synthetic")
     parser.add_argument("--samples", type=int, default=1024)
     parser.add_argument("--outdir", default=os.path.join(os.getcwd(), "runs"))
@@ -122,6 +125,21 @@ def main(argv=None):
         segmentation_model = networks.UnetGenerator(1, 4, 7, ngf=32, norm_layer=functools.partial(torch.nn.BatchNorm2d, affine=True,
                                                     track_running_stats=True), use_dropout='False', dtype=args.dtype).eval()   # train.py:171-175
     state.update({"train_fid": None, "test_fid": None, "inception_model": None, "segmentation_model": segmentation_model})
+    if args.fid_weights:
+        # train.py:154-180: ground-truth statistics of the train and test loaders, once. Every rank computes them on its own shard
+        # (no broadcast: each rank also evaluates its own shard); the ground truths pass the same 8-bit truncation as the composites
+        from gan_inpainting_amd.experiment_list._common import to_device_images
+        from gan_inpainting_amd.lib.fid import fid_score
+        from gan_inpainting_amd.lib.fid.inception import InceptionV3
+        device = torch.device("cuda", torch.cuda.current_device())
+        inception_model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[2048]], dtype=args.dtype)
+        inception_model.load_state_dict(torch.load(args.fid_weights, map_location="cpu"))
+        inception_model = inception_model.to(device).eval()
+        print("Calculating FID statistics")
+        for k in ("train", "test"):
+            grounds = (to_device_images(item[0], device, state) for item in loaders[k])
+            state[k + "_fid"] = fid_score.calculate_activation_statistics(grounds, inception_model, quantize=True)
+        state["inception_model"] = inception_model
     for name in args.experiments:
         exp = importlib.import_module(f"gan_inpainting_amd.experiment_list.{name}")
         exp.begin(state, loaders)

@@ -375,6 +375,37 @@ int gi_vgg19_perceptual_style(gi_vgg* v, const float* output, const float* targe
 /* feature map of tap 0..4 as (n,C,h,w) fp32 (parity checks) */
 int gi_vgg19_features(gi_vgg* v, const float* x, int n, int tap, float* out_nchw);
 
+/* ---- Frechet Inception Distance (reference lib/fid/): Inception-V3 pool3 features + streaming statistics ----
+ * The FID variant of Inception-V3 (lib/fid/inception.py: average pools that do not count padding in Mixed_5b..5d,
+ * 6b..6e, 7b; a max pool in Mixed_7c), forward only, up to the 2048-wide global average (output block 3).
+ * dtype GI_F16 / GI_F32 is the compute type (MFMA, fp32 accumulation). params: fp32, the published state
+ * dict's layout per BasicConv2d: "<layer>.conv.weight" (O,I,kh,kw), "<layer>.bn.weight|bias|running_mean|
+ * running_var" (gi_inception_tensor_desc: name, shape, float offset); BatchNorm (eps 0.001, running statistics)
+ * is folded into weight and bias by gi_inception_sync_weights. ctx may be NULL for the inventory alone
+ * (param_floats / num_tensors / tensor_desc / workspace_bytes); every other call on such a handle fails. */
+typedef struct gi_inception gi_inception;
+int gi_inception_create(gi_ctx* ctx, int dtype, int max_batch, gi_inception** out);
+void gi_inception_destroy(gi_inception* v);
+int64_t gi_inception_param_floats(const gi_inception* v);
+int64_t gi_inception_workspace_bytes(const gi_inception* v);
+int gi_inception_num_tensors(const gi_inception* v);
+int gi_inception_tensor_desc(const gi_inception* v, int index, char* name, int name_cap, int* shape4, int64_t* offset);
+int gi_inception_bind(gi_inception* v, const float* params, void* ws, int64_t ws_bytes);   /* ws 256-byte aligned */
+int gi_inception_sync_weights(gi_inception* v);                                            /* after params change */
+/* x: (n,c,H,W) fp32 in [0,1], c = 1 (replicated over 3 channels) or 3, any H, W: resized to 299x299 (bilinear,
+ * align_corners = False) and mapped to 2x - 1 on the device. out: (n,2048) fp32. n <= max_batch. */
+int gi_inception_features(gi_inception* v, const float* x, int n, int c, int H, int W, float* out);
+/* runs the input kernel and the first nconvs convolutions (with the pools between them) only: tests read
+ * gi_debug_last_kernel() to see which kernel served convolution nconvs - 1 */
+int gi_inception_debug_forward_convs(gi_inception* v, const float* x, int n, int c, int H, int W, int nconvs);
+/* Streaming mean / covariance of d-wide fp32 feature rows in fp64 (lib/fid/fid_score.py:202-203 np.mean /
+ * np.cov(rowvar=False)). acc: gi_fid_stats_acc_doubles(d) = 1 + d + d*d device doubles {count, sum, X^T X},
+ * zeroed by the caller before the first update. Every element is accumulated row by row in arrival order, so
+ * the result does not depend on how the rows were split into calls. finish: mu (d), sigma (d,d), divisor n-1. */
+int64_t gi_fid_stats_acc_doubles(int d);
+int gi_fid_stats_update(gi_ctx* ctx, double* acc, const float* feats, int n, int d);
+int gi_fid_stats_finish(gi_ctx* ctx, const double* acc, double* mu, double* sigma, int d);
+
 /* ---- input transform: transforms.Resize(size) + ToTensor() of train.py:69-72 on decoded
  *      8-bit grey images (lib/data/dataset.py:6-12). Bit-exact restatement of Pillow's antialiased bilinear
  *      resampler (22-bit fixed point, horizontal pass first, uint8 intermediate), then /255. ------------- */
