@@ -68,7 +68,69 @@ def _act(z, slope, flip=None):
     return torch.where(pos, z, slope * z)
 
 
-def unet_forward(P, x, num_downs=7, train=True, dropout_masks=None, norm="batch", taps=None, flips=None):
+class _Store16(torch.autograd.Function):
+    """One write of a tensor of the compute type to memory by the fp16 engine: the value is rounded to fp16 (forward,
+    `fwd`) and so is the gradient that arrives for it (backward, `bwd`: the engine keeps its gradient tensors in fp16 too;
+    the parity tests run with set_loss_scale(1.0), so no scale enters). The arithmetic around it stays in x.dtype."""
+
+    @staticmethod
+    def forward(ctx, x, fwd, bwd):
+        ctx.bwd = bwd
+        return x.half().to(x.dtype) if fwd else x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g.half().to(g.dtype) if ctx.bwd else g), None, None
+
+
+def store_fp16(x, fwd=True, bwd=True):
+    """The `store` of unet_forward / patchgan_forward for the fp16 engine. fwd / bwd select the direction(s) in which the
+    engine has a tensor in memory at that point: a tensor read by two consumers has ONE stored value but TWO stored gradients
+    (one per consumer, added in fp32 by the kernel that reads them), and weights are rounded once while their gradients are
+    accumulated in fp32."""
+    return _Store16.apply(x, fwd, bwd)
+
+
+def _w16(P, key, store):
+    """A 4x4 weight as the engine's kernels read it: the packed copies of type T (gi_pack_weights; the single-channel layers
+    and the critic head convert their fp32 rows to fp16 MFMA fragments in registers: c1_gather_mfma_kernel, c1_col_kernel,
+    head_fwd512_kernel). The gradient is accumulated in fp32 into the master buffer: not rounded."""
+    return P[key] if store is None else store(P[key], True, False)
+
+
+def _bn_stored(P, prefix, raw, train, store):
+    """BatchNorm2d over a convolution output the engine has stored: the batch statistics come from the GEMM epilogue's fp32
+    accumulators, i.e. from the UNROUNDED sums (igemm*_kernel epilogue -> stat_acc.h; bn_finalize), the normalisation pass
+    then reads the stored (rounded) tensor (bn_apply_acc_kernel / bn_apply_kernel, or the folded finisher of igemm7).
+    F.batch_norm would take the statistics from the tensor it normalises, so this is written out. Backward: the gradient at the
+    convolution output is written once, after the whole BatchNorm backward (act_bn_bwd_kernel -> dz): one bwd store on raw."""
+    raw = store(raw, False, True)                                # dz: act_bn_bwd_kernel
+    stored = raw + (store(raw.detach(), True, False) - raw.detach())   # value: the igemm epilogue's store; gradient: identity
+    if train:
+        P[prefix + ".num_batches_tracked"] += 1
+        mean = raw.mean((0, 2, 3))
+        var = raw.var((0, 2, 3), unbiased=False)
+        n = raw.numel() // raw.shape[1]
+        with torch.no_grad():
+            P[prefix + ".running_mean"].mul_(1 - BN_MOMENTUM).add_(BN_MOMENTUM * mean)
+            P[prefix + ".running_var"].mul_(1 - BN_MOMENTUM).add_(BN_MOMENTUM * var * (n / max(n - 1, 1)))
+    else:
+        mean, var = P[prefix + ".running_mean"], P[prefix + ".running_var"]
+    inv = torch.rsqrt(var + BN_EPS)
+    v = lambda t: t.view(1, -1, 1, 1)   # noqa: E731
+    return (stored - v(mean)) * v(inv * P[prefix + ".weight"]) + v(P[prefix + ".bias"])
+
+
+def _norm_stored(P, prefix, raw, train, norm, store):
+    """_norm with the engine's fp16 stores. InstanceNorm / no norm (unet_forward_plain): the GEMM has no statistics epilogue
+    there, in_forward_kernel takes mean and variance from the stored tensor - statistics of ROUNDED values, unlike BatchNorm."""
+    if norm == "batch":
+        return _bn_stored(P, prefix, raw, train, store)
+    raw = store(raw, True, True)                                 # igemm epilogue (value) / act_bn_bwd_kernel (dz)
+    return F.instance_norm(raw, eps=BN_EPS) if norm == "instance" else raw
+
+
+def unet_forward(P, x, num_downs=7, train=True, dropout_masks=None, norm="batch", taps=None, flips=None, store=None):
     """UnetGenerator.forward (networks.py:246-253) through the recursive
     UnetSkipConnectionBlock.forward (networks.py:320-324), unrolled.
 
@@ -84,7 +146,12 @@ def unet_forward(P, x, num_downs=7, train=True, dropout_masks=None, norm="batch"
     downrelu = output of level k's down path) and 'u<k>' (level k's up-path output before dropout, one half of the next
     uprelu's input; the other half is the skip, whose kinks are those of 'd<k-1>'), together with the keep-mask under
     'u<k>.keep' where dropout follows (tools/pick_kink_safe_seeds.py). flips: {tap name: bool tensor}, see _act.
+    store: None (this code path, bit for bit what it was) or a callable store(t, fwd, bwd) such as store_fp16: the storage-rounded
+    restatement _unet_forward_stored below.
     """
+    if store is not None:
+        assert not flips, "the storage-rounded restatement takes its own kink decisions"
+        return _unet_forward_stored(P, x, num_downs, train, dropout_masks, norm, taps, store)
     flips = flips or {}
     keys = _p.unet_key_layout(num_downs)
     drops = _p.dropout_levels(num_downs)
@@ -120,9 +187,80 @@ def unet_forward(P, x, num_downs=7, train=True, dropout_masks=None, norm="batch"
     return torch.tanh(u)
 
 
-def patchgan_forward(P, x, sigmoid=True, train=True, taps=None, flips=None):
+def _unet_forward_stored(P, x, num_downs, train, dropout_masks, norm, taps, store):
+    """unet_forward with a `store` at every point where the engine writes a tensor of the compute type (csrc/net.hip:
+    unet_forward / unet_backward, default options). Same graph, same taps (the pre-activations themselves are never in
+    memory: a tap is what the normalisation pass computes in fp32 before it applies the activation and rounds)."""
+    keys = _p.unet_key_layout(num_downs)
+    drops = _p.dropout_levels(num_downs)
+    W = lambda key: _w16(P, key + ".weight", store)   # noqa: E731
+    skips = {}
+    N, _, H, Wd = x.shape
+    # d1 as unfold + GEMM, the form the engine runs it in. The image is an fp16 MFMA operand (c1_gather_mfma_kernel; d1's weight
+    # gradient reads it the same way: c1_wgrad_mfma_kernel). The input gradient is the overlap-add of an fp16 `col` tensor
+    # (c1_col_kernel / c1_scatter_fused_kernel): the bwd store on the unfolded columns; dx itself is fp32.
+    cols = store(F.unfold(store(x, True, False), 4, stride=2, padding=1), False, True)
+    h = torch.einsum("ct,ntl->ncl", W(keys[0]["down"]).reshape(-1, 16), cols).reshape(N, -1, H // 2, Wd // 2)
+    if P.get(keys[0]["down"] + ".bias") is not None:
+        h = h + P[keys[0]["down"] + ".bias"].view(1, -1, 1, 1)
+    # the gradient at d1's output is written once, by the epilogue of d2's input-gradient GEMM, which adds the skip gradient and
+    # applies LeakyReLU' to its fp32 accumulators (igemm mask epilogue, lrelu1_done); without that fusion the GEMM's own output
+    # would be rounded first (act_bn_bwd_kernel then reads two fp16 tensors): not modelled
+    h = store(h, False, True)
+    for k in range(2, num_downs + 1):
+        if taps is not None:
+            taps[f"d{k - 1}"] = h
+        s = store(F.leaky_relu(h, 0.2), True, False)     # a_{k-1}: c1_gather_mfma_kernel (k = 2), bn_apply*_kernel / in_forward_kernel
+        # one stored value, two stored gradients: the concat buffer's skip half (written by up_{k-1}'s input-gradient GEMM, or by
+        # c1_gather_mfma_kernel for level 1) and d_k's input gradient (igemm epilogue); act_bn_bwd_kernel adds them in fp32
+        skips[k - 1] = store(s, False, True)
+        sc = s if k == 2 and norm == "batch" else store(s, False, True)
+        h = F.conv2d(sc, W(keys[k - 1]["down"]), P.get(keys[k - 1]["down"] + ".bias"), stride=2, padding=1)
+        if keys[k - 1]["dnorm"]:
+            h = _norm_stored(P, keys[k - 1]["dnorm"], h, train, norm, store)
+    if taps is not None:
+        taps[f"d{num_downs}"] = h
+    # innermost: the uprelu runs in the convolution's epilogue, the tensor in memory is relu(conv) (igemm epilogue, GI_ACT_RELU);
+    # its gradient is up_nd's input gradient (igemm epilogue), masked by [E > 0] without further rounding
+    u = store(F.relu(h), True, True)
+    for k in range(num_downs, 0, -1):
+        # the decoder half is stored already ReLU-ed (below); the skip half's ReLU is applied to the operand as it is read
+        inp = u if k == num_downs else torch.cat([F.relu(skips[k]), u], 1)
+        if k == 1:
+            break
+        u = F.conv_transpose2d(inp, W(keys[k - 1]["up"]), P.get(keys[k - 1]["up"] + ".bias"), stride=2, padding=1)
+        if keys[k - 1]["unorm"]:
+            u = _norm_stored(P, keys[k - 1]["unorm"], u, train, norm, store)
+        if taps is not None:
+            taps[f"u{k}"] = u
+        if train and k in drops:
+            if taps is not None:
+                taps[f"u{k}.keep"] = dropout_masks[k]
+            u = u * dropout_masks[k].to(u.dtype) * 2.0
+        # the reference applies the parent's in-place ReLU to the concat later; the engine's normalisation pass stores relu(u) after
+        # dropout (the tensor is only ever read through that ReLU): same value, rounded here (bn_apply*_kernel / in_forward_kernel;
+        # level 2 with the fused head: c1_col_kernel's on-the-fly operand, same expression and rounding). Gradient: the concat
+        # buffer's decoder half, written by up_{k-1}'s input-gradient GEMM (level 2: c1_gather_mfma_kernel)
+        u = store(F.relu(u), True, True)
+    # u1 = ConvTranspose2d(2 ngf -> 1) as the engine runs it: col[p][tap] on the MFMA, ROUNDED to fp16 (c1_col_kernel /
+    # c1_scatter_fused_kernel), then the overlap-add with bias and tanh in fp32. The reference's conv_transpose2d has no such
+    # intermediate. Backward: tanh' in fp32 (tanh_bwd_kernel); the bias gradient sums that fp32 tensor, the input gradient and the
+    # weight gradient read it as an fp16 MFMA operand (c1_gather_mfma_kernel, c1_wgrad_mfma_kernel): the bwd store before the bias
+    col = store(torch.einsum("ct,ncl->ntl", W(keys[0]["up"]).reshape(-1, 16), inp.reshape(N, inp.shape[1], -1)), True, False)
+    y = store(F.fold(col, (H, Wd), 4, stride=2, padding=1), False, True)
+    bias = P.get(keys[0]["up"] + ".bias")
+    if bias is not None:
+        y = y + bias.view(1, -1, 1, 1)
+    return torch.tanh(y)
+
+
+def patchgan_forward(P, x, sigmoid=True, train=True, taps=None, flips=None, store=None):
     """PatchGANDiscriminator.forward (networks.py:335-363); Linear(25,1) generalised to
-    Linear((H/16-3)*(W/16-3),1) for sizes other than 128x128."""
+    Linear((H/16-3)*(W/16-3),1) for sizes other than 128x128.
+    store: as in unet_forward (None: this code path unchanged)."""
+    if store is not None:
+        assert not flips, "the storage-rounded restatement takes its own kink decisions"
+        return _patchgan_forward_stored(P, x, sigmoid, train, taps, store)
     h = F.conv2d(x, P["model.0.weight"], None, stride=2, padding=1)
     if taps is not None:   # the tensors that feed a LeakyReLU kink (tools/pick_kink_safe_seeds.py)
         taps["c1"] = h
@@ -135,6 +273,35 @@ def patchgan_forward(P, x, sigmoid=True, train=True, taps=None, flips=None):
             taps[f"c{i + 2}"] = h
         h = _act(h, 0.2, flips.get(f"c{i + 2}"))
     h = F.conv2d(h, P["model.11.weight"], None, stride=1, padding=0)
+    h = h.reshape(h.shape[0], -1)
+    h = F.linear(h, P["model.13.weight"], P["model.13.bias"])
+    if sigmoid:
+        h = torch.sigmoid(h)
+    return h.view(-1, 1)
+
+
+def _patchgan_forward_stored(P, x, sigmoid, train, taps, store):
+    """patchgan_forward with a `store` wherever the engine writes a tensor of the compute type (csrc/net.hip: patchgan_forward /
+    patchgan_backward, default options)."""
+    N, _, H, Wd = x.shape
+    # conv1 = the generator's d1: fp16 image operand, input gradient through an fp16 col tensor (see _unet_forward_stored)
+    cols = store(F.unfold(store(x, True, False), 4, stride=2, padding=1), False, True)
+    h = torch.einsum("ct,ntl->ncl", _w16(P, "model.0.weight", store).reshape(-1, 16), cols).reshape(N, -1, H // 2, Wd // 2)
+    h = store(h, False, True)          # the gradient at conv1's output: epilogue of conv2's input-gradient GEMM (LeakyReLU' on fp32 accumulators)
+    if taps is not None:
+        taps["c1"] = h
+    h = store(F.leaky_relu(h, 0.2), True, False)   # c1_gather_mfma_kernel
+    for i, (conv, bn) in enumerate(((2, 3), (5, 6), (8, 9))):
+        h = F.conv2d(h, _w16(P, f"model.{conv}.weight", store), None, stride=2, padding=1)
+        h = _bn_stored(P, f"model.{bn}", h, train, store)
+        if taps is not None:
+            taps[f"c{i + 2}"] = h
+        # bn_apply*_kernel; conv4 with the fused head: head_fwd512_kernel's on-the-fly fp16 operand (same expression, same rounding).
+        # Gradient: conv_{i+3}'s input-gradient GEMM epilogue / head_bwd512_kernel (da4), one consumer each
+        h = store(F.leaky_relu(h, 0.2), True, True)
+    # head: Conv2d(512 -> 1, 4x4) on fp16 fragments with fp32 accumulation, then everything in fp32 (head_fwd512_kernel, head_h512_kernel):
+    # no store between the 4x4 convolution, the Linear and the sigmoid
+    h = F.conv2d(h, _w16(P, "model.11.weight", store), None, stride=1, padding=0)
     h = h.reshape(h.shape[0], -1)
     h = F.linear(h, P["model.13.weight"], P["model.13.bias"])
     if sigmoid:

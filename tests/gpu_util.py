@@ -1,5 +1,7 @@
 """Shared helpers for the -m gpu tests (layout conversion, C-ABI calls, error reports)."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import torch
@@ -66,14 +68,52 @@ def hip_decisions(net, case):
     return {name: (net.saved_activation(kind, level, shape) > 0).cpu() for name, (shape, kind, level) in kink.tap_shapes(case).items()}
 
 
-def check_grads_vs_kink_reference(what, net, case, dx, dtype, tol_max, tol_l2=None, skip=()):
+PARITY_OUT = os.environ.get("GI_PARITY_OUT", "")
+
+
+def record(key, value):
+    """As tests/test_fid_gpu.py::_record: when GI_PARITY_OUT names a file, the figures of this run are collected there."""
+    if PARITY_OUT:
+        d = json.load(open(PARITY_OUT)) if os.path.exists(PARITY_OUT) else {}
+        d[key] = value
+        json.dump(d, open(PARITY_OUT, "w"), indent=1, sort_keys=True)
+
+
+def check_fp16_vs_yardstick(what, net, case, ref, rep, y=None, dx=None, skip=()):
+    """fp16 only, next to the absolute bounds: every tensor - output and running statistics (when y is given), every activation
+    gi_net_saved_activation exposes, every parameter gradient, dx - may err at most oracle.kink.K times what the storage-rounded
+    restatement of the oracle errs on the same tensor (oracle.kink.yardstick / fp16_parity), and the band holds at most 5 % of the
+    live units. ref, rep: kink_reference's result for the HIP forward's decisions. Prints and records every ratio."""
+    from oracle import kink
+    impl = {"acts": {name: net.saved_activation(kind, level, shape).cpu() for name, (shape, kind, level) in kink.tap_shapes(case).items()},
+            "grads": {n: p.grad.detach().cpu() for n, p in net.named_parameters() if n not in skip}}
+    if dx is not None:
+        impl["dx"] = dx.detach().cpu()
+    if y is not None:
+        impl["y"] = y.detach().cpu()
+        impl["stats"] = {k: v.detach().cpu() for k, v in net.state_dict().items() if k.endswith("running_mean") or k.endswith("running_var")}
+    records, bad = kink.fp16_parity(case, impl, ref, rep, skip)
+    for r in records:
+        print(f"{what} yardstick {r['cls']} {r['name']}: HIP {r['err']:.3e} restatement {r['yardstick']:.3e} ratio {r['ratio']:.2f}")
+    share = rep["at_risk"] / max(rep["units"], 1)
+    print(f"{what}: {share:.2%} of the live units inside the fp16 band, {rep['flipped'] / max(rep['units'], 1):.2e} decided by the HIP forward")
+    record(what, {"band_share": share, "flipped_share": rep["flipped"] / max(rep["units"], 1),
+                  "worst": {c: {k: r[k] for k in ("name", "err", "yardstick", "ratio")} for c, r in kink.worst_by_class(records).items()},
+                  "tensors": {f"{r['cls']} {r['name']}": [r["err"], r["yardstick"], r["ratio"]] for r in records}})
+    assert not bad, f"{what}:\n" + "\n".join(bad)
+
+
+def check_grads_vs_kink_reference(what, net, case, dx, dtype, tol_max, tol_l2=None, skip=(), y=None):
     """Every parameter gradient of `net` (and dx) against the fp64 oracle evaluated with the HIP forward's own kink
     decisions on the units the oracle itself marks as undecidable (oracle/kink.py). fp32: max-norm <= tol_max * max|ref| per
     tensor; fp16 (tol_l2 given): relative L2 <= tol_l2 per tensor. Asserts that no kink decision differs outside the band.
+    fp16 additionally: check_fp16_vs_yardstick on the same reference (with the output and the running statistics when y is given).
     Returns the report."""
     from oracle import kink
     fp16 = dtype == "fp16"
     y64, g64, dx64, rep = kink.kink_reference(case, hip_decisions(net, case), fp16=fp16)
+    if fp16:
+        print(f"{what}: {rep['at_risk'] / max(rep['units'], 1):.2%} of the live units inside the fp16 band")
     print(f"{what}: {rep['units']} kink inputs, {rep['at_risk']} within the band, {rep['flipped']} decided by the HIP forward, "
           f"{rep['outside']} disagreements outside the band (worst {rep['outside_worst']:.2f} band widths)")
     assert rep["outside"] == 0, f"{what}: {rep['outside']} kink decisions differ from the oracle's outside the rounding band"
@@ -98,6 +138,8 @@ def check_grads_vs_kink_reference(what, net, case, dx, dtype, tol_max, tol_l2=No
             bad.append(f"{what} grad {name}: {'relL2' if tol_l2 is not None else 'max-norm'} error {err:.3e} > {tol:.1e}")
     print(f"{what}: worst gradient error {worst[0]:.3e} at {worst[1]}")
     assert not bad, "\n".join(bad)
+    if fp16:
+        check_fp16_vs_yardstick(what, net, case, (y64, g64, dx64), rep, y, dx, skip)
     return rep, y64
 
 

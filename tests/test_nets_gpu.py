@@ -25,6 +25,10 @@ TOL_OUT = {"fp32": 1e-4, "fp16": 2e-2}
 # Measured on MI355X (round 3, all cases of this file and tests/test_norms_gpu.py): fp32 worst 1.6e-5 with 0..10 units decided
 # by the HIP forward out of 0.5..31 M; fp16 worst relative L2 1.7e-2. The bounds: 1e-4 (ten times tighter than north_star's
 # 1e-3) and 3e-2.
+# fp16, next to these absolute bounds (gpu_util.check_fp16_vs_yardstick, oracle/kink.py): output, running statistics, every saved
+# activation, every gradient <= K = 4 times the error of the oracle's own storage-rounded restatement on the same tensor - a
+# critic gradient off by 1 % passes 3e-2 and fails that (tests/test_yardstick_cpu.py). Measured ratios: DESIGN.md section 2,
+# profiles/r07_fp16_yardstick.json.
 TOL_GRAD = {"fp32": 1e-4, "fp16": None}
 TOL_GRAD_L2 = {"fp32": None, "fp16": 3e-2}
 TOL_ABSMEAN = {"fp32": 1e-3, "fp16": 6e-2}   # per-tensor mean|grad| against the numbers recorded from the reference
@@ -74,7 +78,7 @@ def test_unet_forward_backward_vs_oracle(dtype, cfg):
             assert ok, msg
         if k.endswith("num_batches_tracked"):
             assert int(v) == 1
-    check_grads_vs_kink_reference(what, net, case, xd.grad, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype])
+    check_grads_vs_kink_reference(what, net, case, xd.grad, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype], y=y)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "fp16"])
@@ -227,7 +231,7 @@ def test_patchgan_vs_oracle(dtype, cfg):
         if k.endswith("running_mean") or k.endswith("running_var"):
             ok, msg = report(f"{what} {k}", v.cpu(), OP[k], 1e-4 if dtype == "fp32" else 2e-2)
             assert ok, msg
-    check_grads_vs_kink_reference(what, net, case, xd.grad, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype])
+    check_grads_vs_kink_reference(what, net, case, xd.grad, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype], y=y)
     if HW == 128:
         fx = load("patchgan128")   # recorded from the reference with seed 21; only check shape contract here
         assert fx["out_sig"].shape[1] == 1
@@ -377,7 +381,7 @@ def test_patchgan_two_populations_vs_oracle(dtype, hw, n):
             assert ok, msg
     for _, p in net.named_parameters():   # _backward_raw accumulated into the flat gradient buffer: expose it as .grad
         assert p.grad is not None
-    check_grads_vs_kink_reference(what, net, case, dx, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype])
+    check_grads_vs_kink_reference(what, net, case, dx, dtype, TOL_GRAD[dtype], TOL_GRAD_L2[dtype], y=y)
 
 
 @pytest.mark.parametrize("dtype,hw,n", [("fp32", 256, 2), ("fp16", 256, 4), ("fp32", 128, 2)])

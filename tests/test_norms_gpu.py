@@ -123,7 +123,7 @@ def test_unet_other_norms_vs_oracle(norm, cfg, dtype):
     # num_downs = 8 at 256x256: levels 7 / 8 normalise FOUR values per (image, channel); in fp16 storage the innermost four
     # tensors reach 6.2e-2 relative L2 (measured; smooth ill-conditioning, not kinks: fp32 is at 1.6e-5 on the same case)
     tol_l2 = 1e-1 if (dtype == "fp16" and nd == 8) else TOL_KINK_L2[dtype]
-    check_grads_vs_kink_reference(what, net, case, x.grad, dtype, TOL_KINK[dtype], tol_l2, skip=zero)
+    check_grads_vs_kink_reference(what, net, case, x.grad, dtype, TOL_KINK[dtype], tol_l2, skip=zero, y=y)
     prm = dict(net.named_parameters())
     for name in zero:
         g = prm[name].grad.detach()
