@@ -106,6 +106,10 @@ PROTOTYPES = {
     "gi_inception_sync_weights": (_i, [_vp]),
     "gi_inception_features": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "gi_inception_debug_forward_convs": (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    "gi_inception_num_steps": (_i, [_vp]),
+    "gi_inception_step_desc": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gi_inception_debug_forward_steps": (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
+    "gi_inception_debug_read": (_i, [_vp, _i, _i, _i, _vp]),
     "gi_fid_stats_acc_doubles": (_i64, [_i]),
     "gi_fid_stats_update": (_i, [_vp, _vp, _vp, _i, _i]),
     "gi_fid_stats_finish": (_i, [_vp, _vp, _vp, _vp, _i]),

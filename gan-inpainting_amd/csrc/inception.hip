@@ -303,6 +303,19 @@ __global__ void __launch_bounds__(256) inc_gap_kernel(const T* __restrict__ in, 
   }
 }
 
+// debug read-back: channels [coff, coff + C) of the ld-wide NHWC rows of n HW-pixel maps -> (n, C, HW) fp32 (every T is exact in fp32)
+template <typename T>
+__global__ void __launch_bounds__(256) inc_export_kernel(const T* __restrict__ in, float* __restrict__ out, int n, int HW, int C, int ld, int coff) {
+  const int64_t total = (int64_t)n * C * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int q = (int)(i % HW);
+    const int64_t t = i / HW;
+    const int ch = (int)(t % C);
+    const int64_t img = t / C;
+    out[i] = (float)in[(img * HW + q) * ld + coff + ch];
+  }
+}
+
 // BasicConv2d = conv (no bias) + BatchNorm(eps 0.001, running statistics) + ReLU, folded in fp32:
 // wp[o][tap][ci] = w[o][ci][tap] * g[o] / sqrt(var[o] + eps) (ci >= cin: 0), bias[o] = beta[o] - mean[o] * g[o] / sqrt(var[o] + eps)
 template <typename T>
@@ -382,6 +395,7 @@ struct gi_inception {
   std::vector<void*> wpk;
   std::vector<float*> bias;
   bool bound, synced;
+  int dbg_steps, dbg_n;            // the last call was debug_forward_steps(dbg_steps) on dbg_n images (-1: it was not): what debug_read may read
 };
 
 namespace {
@@ -541,15 +555,16 @@ int inc_conv_launch(gi_inception* v, const IncStep& s, int n) {
   return GI_OK;
 }
 
-// runs the program; nconvs >= 0: stops after that many convolutions (and writes no features)
+// runs the program; nconvs >= 0: stops after that many convolutions, nsteps >= 0: after that many steps (either writes no features)
 template <typename T>
-int inc_run(gi_inception* v, const float* x, int n, int c, int H, int W, float* out, int nconvs) {
+int inc_run(gi_inception* v, const float* x, int n, int c, int H, int W, float* out, int nconvs, int nsteps = -1) {
   hipStream_t st = v->ctx->stream;
   hipLaunchKernelGGL((inc_input_kernel<T>), dim3(inc_grid((int64_t)n * INC_HW * INC_HW)), dim3(256), 0, st, x, n, c, H, W, (T*)v->in8);
   GI_LAUNCH_CHECK();
-  int done = 0;
+  int done = 0, ran = 0;
   for (const IncStep& s : v->steps) {
     if (nconvs >= 0 && done >= nconvs) return GI_OK;
+    if (nsteps >= 0 && ran++ >= nsteps) return GI_OK;
     if (s.kind == INC_OP_CONV) {
       GI_TRY(inc_conv_launch<T>(v, s, n));
       ++done;
@@ -566,13 +581,16 @@ int inc_run(gi_inception* v, const float* x, int n, int c, int H, int W, float* 
       hipLaunchKernelGGL((inc_pool3s1_kernel<T, true>), dim3(grid), dim3(256), 0, st, in, o, n, s.H, s.W, s.C);
     GI_LAUNCH_CHECK();
   }
-  if (nconvs >= 0) return GI_OK;
+  if (nconvs >= 0 || nsteps >= 0) return GI_OK;
   const IncStep& last = v->steps.back();
   hipLaunchKernelGGL((inc_gap_kernel<T>), dim3(inc_grid((int64_t)n * INC_FEAT)), dim3(256), 0, st, (const T*)v->buf[v->final_buf], out, n,
                      last.Ho * last.Wo, INC_FEAT);
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
+
+// channels of a step's input view: a convolution's cin (step 0: the 8 channels of the padded resized input), a pool's C
+int inc_step_cin(const gi_inception* v, const IncStep& s) { return s.kind != INC_OP_CONV ? s.C : s.src < 0 ? 8 : v->convs[s.conv].cin; }
 
 int inc_check_call(const gi_inception* v, const float* x, int n, int c, int H, int W, const char* who) {
   GI_REQUIRE(v && v->ctx, "%s: the handle was created without a context (inventory only)", who);
@@ -598,6 +616,7 @@ int gi_inception_create(gi_ctx* ctx, int dtype, int max_batch, gi_inception** ou
   bld.v = v;
   bld.build();
   v->params = nullptr; v->ws = nullptr; v->bound = false; v->synced = false;
+  v->dbg_steps = -1; v->dbg_n = 0;
   v->ws_bytes = inc_ws_layout(v, nullptr);
   *out = v;
   return GI_OK;
@@ -627,12 +646,14 @@ int gi_inception_bind(gi_inception* v, const float* params, void* ws, int64_t ws
   v->params = params; v->ws = (char*)ws;
   inc_ws_layout(v, v->ws);
   v->bound = true; v->synced = false;
+  v->dbg_steps = -1;
   return GI_OK;
 }
 
 int gi_inception_sync_weights(gi_inception* v) {
   GI_REQUIRE(v && v->ctx && v->bound, "inception_sync_weights: not bound");
   hipStream_t st = v->ctx->stream;
+  v->dbg_steps = -1;
   for (size_t i = 0; i < v->convs.size(); ++i) {
     const IncConvDesc& c = v->convs[i];
     const int taps = c.kh * c.kw, cinp = (c.cin + 7) / 8 * 8;
@@ -652,13 +673,57 @@ int gi_inception_sync_weights(gi_inception* v) {
 int gi_inception_features(gi_inception* v, const float* x, int n, int c, int H, int W, float* out) {
   GI_TRY(inc_check_call(v, x, n, c, H, W, "inception_features"));
   GI_REQUIRE(out, "inception_features: null output");
+  v->dbg_steps = -1;
   return v->dtype == GI_F16 ? inc_run<half_t>(v, x, n, c, H, W, out, -1) : inc_run<float>(v, x, n, c, H, W, out, -1);
 }
 
 int gi_inception_debug_forward_convs(gi_inception* v, const float* x, int n, int c, int H, int W, int nconvs) {
   GI_TRY(inc_check_call(v, x, n, c, H, W, "inception_debug_forward_convs"));
   GI_REQUIRE(nconvs >= 0 && nconvs <= (int)v->convs.size(), "inception_debug_forward_convs: nconvs=%d (0..%d)", nconvs, (int)v->convs.size());
+  v->dbg_steps = -1;
   return v->dtype == GI_F16 ? inc_run<half_t>(v, x, n, c, H, W, nullptr, nconvs) : inc_run<float>(v, x, n, c, H, W, nullptr, nconvs);
+}
+
+int gi_inception_num_steps(const gi_inception* v) { return v ? (int)v->steps.size() : -1; }
+
+int gi_inception_step_desc(const gi_inception* v, int step, int* kind, int* conv, int* in_chw, int* out_chw, int* route4) {
+  GI_REQUIRE(v && step >= 0 && step < (int)v->steps.size() && kind && conv && in_chw && out_chw && route4, "inception_step_desc: bad argument");
+  const IncStep& s = v->steps[step];
+  *kind = s.kind; *conv = s.conv;
+  in_chw[0] = inc_step_cin(v, s); in_chw[1] = s.H; in_chw[2] = s.W;
+  out_chw[0] = s.C; out_chw[1] = s.Ho; out_chw[2] = s.Wo;
+  route4[0] = s.src; route4[1] = s.dst; route4[2] = s.ldout; route4[3] = s.coffout;
+  return GI_OK;
+}
+
+int gi_inception_debug_forward_steps(gi_inception* v, const float* x, int n, int c, int H, int W, int nsteps) {
+  GI_TRY(inc_check_call(v, x, n, c, H, W, "inception_debug_forward_steps"));
+  GI_REQUIRE(nsteps >= 0 && nsteps <= (int)v->steps.size(), "inception_debug_forward_steps: nsteps=%d (0..%d)", nsteps, (int)v->steps.size());
+  v->dbg_steps = -1;
+  GI_TRY(v->dtype == GI_F16 ? inc_run<half_t>(v, x, n, c, H, W, nullptr, -1, nsteps) : inc_run<float>(v, x, n, c, H, W, nullptr, -1, nsteps));
+  v->dbg_steps = nsteps; v->dbg_n = n;
+  return GI_OK;
+}
+
+int gi_inception_debug_read(gi_inception* v, int step, int which, int n, float* out) {
+  GI_REQUIRE(v && v->ctx, "inception_debug_read: the handle was created without a context (inventory only)");
+  GI_REQUIRE(v->bound && v->synced && out, "inception_debug_read: bind + sync_weights first, non-null output");
+  GI_REQUIRE(step >= 0 && step < (int)v->steps.size() && which >= 0 && which <= 2, "inception_debug_read: step=%d (0..%d) which=%d (0..2)", step,
+             (int)v->steps.size() - 1, which);
+  GI_REQUIRE(v->dbg_steps == step + 1 && v->dbg_n == n, "inception_debug_read: step %d of %d images is readable only directly after "
+             "debug_forward_steps(nsteps=%d) on as many (last debug run: nsteps=%d, n=%d)", step, n, step + 1, v->dbg_steps, v->dbg_n);
+  const IncStep& s = v->steps[step];
+  const void* src = which == 0 ? (s.src < 0 ? v->in8 : v->buf[s.src]) : v->buf[s.dst];
+  const int HW = which == 0 ? s.H * s.W : s.Ho * s.Wo;
+  const int C = which == 0 ? inc_step_cin(v, s) : which == 1 ? s.C : s.ldout;
+  const int ld = which == 0 ? s.ldin : s.ldout, coff = which == 0 ? s.coffin : which == 1 ? s.coffout : 0;
+  const int grid = inc_grid((int64_t)n * C * HW);
+  if (v->dtype == GI_F16)
+    hipLaunchKernelGGL((inc_export_kernel<half_t>), dim3(grid), dim3(256), 0, v->ctx->stream, (const half_t*)src, out, n, HW, C, ld, coff);
+  else
+    hipLaunchKernelGGL((inc_export_kernel<float>), dim3(grid), dim3(256), 0, v->ctx->stream, (const float*)src, out, n, HW, C, ld, coff);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
 }
 
 int64_t gi_fid_stats_acc_doubles(int d) { return d > 0 ? 1 + (int64_t)d + (int64_t)d * d : -1; }

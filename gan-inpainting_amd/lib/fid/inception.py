@@ -61,6 +61,8 @@ class InceptionV3(nn.Module):
         self.register_buffer("flat", torch.zeros(count))
         self._handles = {}
         self._dirty = True
+        self._debug = None
+        self._program = None
 
     # ---- state_dict in the published file's naming -------------------------------------------------------------------------
     def _views(self):
@@ -145,6 +147,57 @@ class InceptionV3(nn.Module):
         x = x.detach().contiguous()
         hd = self._handle(x.device)
         B.check(B.lib().gi_inception_debug_forward_convs(hd, B.ptr(x), x.shape[0], x.shape[1], x.shape[2], x.shape[3], int(nconvs)))
+
+    STEP_KINDS = ("conv", "max_s2", "avg_s1", "max_s1")
+
+    @staticmethod
+    def program():
+        """The forward program, step by step, from a context-free handle (works without a GPU): a list of dicts with kind
+        (STEP_KINDS), conv (index into the 94 convolutions or -1), cin / cout views (C, H, W), src (-1: the resized input),
+        dst, ldout and coffout."""
+        lib = B.lib()
+        hd = C.c_void_p()
+        B.check(lib.gi_inception_create(None, B.GI_F32, 1, C.byref(hd)))
+        try:
+            out = []
+            kind, conv = C.c_int(), C.c_int()
+            i3, o3, r4 = (C.c_int * 3)(), (C.c_int * 3)(), (C.c_int * 4)()
+            for i in range(lib.gi_inception_num_steps(hd)):
+                B.check(lib.gi_inception_step_desc(hd, i, C.cast(C.pointer(kind), C.c_void_p), C.cast(C.pointer(conv), C.c_void_p),
+                                                   C.cast(i3, C.c_void_p), C.cast(o3, C.c_void_p), C.cast(r4, C.c_void_p)))
+                out.append(dict(kind=InceptionV3.STEP_KINDS[kind.value], conv=int(conv.value), in_chw=tuple(int(a) for a in i3),
+                                out_chw=tuple(int(a) for a in o3), src=int(r4[0]), dst=int(r4[1]), ldout=int(r4[2]), coffout=int(r4[3])))
+            return out
+        finally:
+            lib.gi_inception_destroy(hd)
+
+    def debug_forward_steps(self, x, nsteps):
+        """Runs the input kernel and the first nsteps steps of the program (tests: debug_read of step nsteps - 1)."""
+        self._check(x)
+        x = x.detach().contiguous()
+        hd = self._handle(x.device)
+        B.check(B.lib().gi_inception_debug_forward_steps(hd, B.ptr(x), x.shape[0], x.shape[1], x.shape[2], x.shape[3], int(nsteps)))
+        self._debug = (x.device, x.shape[0])
+
+    def debug_read(self, step, which):
+        """fp32 NCHW copy of step's input view (which = 0), output view (1) or whole destination rows (2); only directly after
+        debug_forward_steps(x, step + 1), for that x's batch size."""
+        if self._debug is None:
+            raise B.BackendError("InceptionV3.debug_read: call debug_forward_steps first")
+        dev, n = self._debug
+        hd = self._handle(dev)
+        d = self.program_cached()[step]
+        c, h, w = d["in_chw"] if which == 0 else d["out_chw"]
+        if which == 2:
+            c = d["ldout"]
+        out = torch.empty(n, c, h, w, dtype=torch.float32, device=dev)
+        B.check(B.lib().gi_inception_debug_read(hd, int(step), int(which), n, B.ptr(out)))
+        return out
+
+    def program_cached(self):
+        if self._program is None:
+            self._program = self.program()
+        return self._program
 
     def __del__(self):
         try:

@@ -398,6 +398,20 @@ int gi_inception_features(gi_inception* v, const float* x, int n, int c, int H, 
 /* runs the input kernel and the first nconvs convolutions (with the pools between them) only: tests read
  * gi_debug_last_kernel() to see which kernel served convolution nconvs - 1 */
 int gi_inception_debug_forward_convs(gi_inception* v, const float* x, int n, int c, int H, int W, int nconvs);
+/* Step-level test seam. The forward program has gi_inception_num_steps() = 107 steps in program order: 94
+ * convolutions and 13 pools. step_desc: kind 0 convolution, 1 max pool 3x3 stride 2, 2 average pool 3x3 stride 1
+ * padding 1 (padding not counted), 3 max pool 3x3 stride 1 padding 1; conv: the convolution's index (tensor_desc
+ * index / 5) or -1; in_chw / out_chw: (C, H, W) of the step's input and output view (step 0 reads the resized
+ * input with its 3 channels padded to 8); route4: {source buffer (-1: the resized input), destination buffer,
+ * channels per destination row, channel offset of the output view in that row}. Works on a context-free handle.
+ * debug_forward_steps: the input kernel and the first nsteps steps (0: the input kernel alone).
+ * debug_read: fp32 NCHW copy (exact) of step's input view (which = 0), output view (1) or whole destination rows
+ * (2: all route4[2] channels). Valid only directly after debug_forward_steps(..., nsteps = step + 1) on the same
+ * n; anything else is refused on the host before any launch. */
+int gi_inception_num_steps(const gi_inception* v);
+int gi_inception_step_desc(const gi_inception* v, int step, int* kind, int* conv, int* in_chw, int* out_chw, int* route4);
+int gi_inception_debug_forward_steps(gi_inception* v, const float* x, int n, int c, int H, int W, int nsteps);
+int gi_inception_debug_read(gi_inception* v, int step, int which, int n, float* out_nchw_f32);
 /* Streaming mean / covariance of d-wide fp32 feature rows in fp64 (lib/fid/fid_score.py:202-203 np.mean /
  * np.cov(rowvar=False)). acc: gi_fid_stats_acc_doubles(d) = 1 + d + d*d device doubles {count, sum, X^T X},
  * zeroed by the caller before the first update. Every element is accumulated row by row in arrival order, so

@@ -226,3 +226,254 @@ def forward(T, x, round_fn=None, blocks=None):
     if blocks is not None:
         blocks["Mixed_7c"] = a
     return a.mean(dim=(2, 3))
+
+
+# ---- the step-level tier ---------------------------------------------------------------------------------------------------------
+# The engine runs the network as a program of 107 steps (94 convolutions, 13 pools) over four activation buffers: 0 / 1 hold a
+# block's input and its concatenated output in turn, 2 / 3 are branch temporaries; a branch's last convolution writes at its channel
+# offset of the block's output rows, so no concatenation pass exists. steps() restates that program from the public architecture.
+U32 = 2.0 ** -24          # unit roundoff of fp32
+
+
+def make_params_exact_fold(seed):
+    """make_params(seed) with every convolution weight rounded to fp16 (exact in both compute types), bn.weight = 1 and
+    bn.running_var = float32(0.999): fl32(0.999f + 0.001f) == 1.0f, so the folded scale is exactly 1, the folded weight is the weight
+    itself and the folded bias is fl32(beta - mean) however the expression is contracted."""
+    P = make_params(seed)
+    for name, *_ in CONVS:
+        w = P[f"{name}.conv.weight"]
+        P[f"{name}.conv.weight"] = w.astype(np.float16).astype(np.float32)
+        P[f"{name}.bn.weight"] = np.ones_like(P[f"{name}.bn.weight"])
+        P[f"{name}.bn.running_var"] = np.full_like(P[f"{name}.bn.running_var"], np.float32(0.999))
+    return P
+
+
+def steps():
+    """The 107-step program: dicts with kind ("conv", "max_s2", "avg_s1", "max_s1"), name / conv (the convolution and its index in
+    CONVS, or None / -1), src (-1: the resized 8-channel input) / dst buffer, in_chw / out_chw (the views), ldout (channels of a
+    destination row) and coffout (where the output view starts in it)."""
+    out, hw = [], {-1: (299, 299)}
+    index = {c[0]: i for i, c in enumerate(CONVS)}
+
+    def conv(name, src, dst, ldout=None, coffout=0):
+        _, cin, cout, (kh, kw), st, (ph, pw) = CONV_BY_NAME[name]
+        h, w = hw[src]
+        ho, wo = (h + 2 * ph - kh) // st + 1, (w + 2 * pw - kw) // st + 1
+        out.append(dict(kind="conv", name=name, conv=index[name], src=src, dst=dst, in_chw=(8 if src < 0 else cin, h, w),
+                        out_chw=(cout, ho, wo), ldout=cout if ldout is None else ldout, coffout=coffout))
+        hw[dst] = (ho, wo)
+
+    def pool(kind, src, c, dst, ldout=None, coffout=0):
+        h, w = hw[src]
+        ho, wo = ((h - 3) // 2 + 1, (w - 3) // 2 + 1) if kind == "max_s2" else (h, w)
+        out.append(dict(kind=kind, name=None, conv=-1, src=src, dst=dst, in_chw=(c, h, w), out_chw=(c, ho, wo),
+                        ldout=c if ldout is None else ldout, coffout=coffout))
+        hw[dst] = (ho, wo)
+
+    conv("Conv2d_1a_3x3", -1, 0)
+    conv("Conv2d_2a_3x3", 0, 1)
+    conv("Conv2d_2b_3x3", 1, 0)
+    pool("max_s2", 0, 64, 1)
+    conv("Conv2d_3b_1x1", 1, 0)
+    conv("Conv2d_4a_3x3", 0, 1)
+    pool("max_s2", 1, 192, 0)
+    x = 0
+    for n, c, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        y, ld = x ^ 1, 224 + pf
+        conv(f"{n}.branch1x1", x, y, ld, 0)
+        conv(f"{n}.branch5x5_1", x, 2)
+        conv(f"{n}.branch5x5_2", 2, y, ld, 64)
+        conv(f"{n}.branch3x3dbl_1", x, 2)
+        conv(f"{n}.branch3x3dbl_2", 2, 3)
+        conv(f"{n}.branch3x3dbl_3", 3, y, ld, 128)
+        pool("avg_s1", x, c, 2)
+        conv(f"{n}.branch_pool", 2, y, ld, 224)
+        x = y
+    n, y = "Mixed_6a", x ^ 1
+    conv(f"{n}.branch3x3", x, y, 768, 0)
+    conv(f"{n}.branch3x3dbl_1", x, 2)
+    conv(f"{n}.branch3x3dbl_2", 2, 3)
+    conv(f"{n}.branch3x3dbl_3", 3, y, 768, 384)
+    pool("max_s2", x, 288, y, 768, 480)
+    x = y
+    for n in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
+        y = x ^ 1
+        conv(f"{n}.branch1x1", x, y, 768, 0)
+        conv(f"{n}.branch7x7_1", x, 2)
+        conv(f"{n}.branch7x7_2", 2, 3)
+        conv(f"{n}.branch7x7_3", 3, y, 768, 192)
+        conv(f"{n}.branch7x7dbl_1", x, 2)
+        conv(f"{n}.branch7x7dbl_2", 2, 3)
+        conv(f"{n}.branch7x7dbl_3", 3, 2)
+        conv(f"{n}.branch7x7dbl_4", 2, 3)
+        conv(f"{n}.branch7x7dbl_5", 3, y, 768, 384)
+        pool("avg_s1", x, 768, 2)
+        conv(f"{n}.branch_pool", 2, y, 768, 576)
+        x = y
+    n, y = "Mixed_7a", x ^ 1
+    conv(f"{n}.branch3x3_1", x, 2)
+    conv(f"{n}.branch3x3_2", 2, y, 1280, 0)
+    conv(f"{n}.branch7x7x3_1", x, 2)
+    conv(f"{n}.branch7x7x3_2", 2, 3)
+    conv(f"{n}.branch7x7x3_3", 3, 2)
+    conv(f"{n}.branch7x7x3_4", 2, y, 1280, 320)
+    pool("max_s2", x, 768, y, 1280, 512)
+    x = y
+    for n, c in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        y = x ^ 1
+        conv(f"{n}.branch1x1", x, y, 2048, 0)
+        conv(f"{n}.branch3x3_1", x, 2)
+        conv(f"{n}.branch3x3_2a", 2, y, 2048, 320)
+        conv(f"{n}.branch3x3_2b", 2, y, 2048, 704)
+        conv(f"{n}.branch3x3dbl_1", x, 2)
+        conv(f"{n}.branch3x3dbl_2", 2, 3)
+        conv(f"{n}.branch3x3dbl_3a", 3, y, 2048, 1088)
+        conv(f"{n}.branch3x3dbl_3b", 3, y, 2048, 1472)
+        pool("avg_s1" if n == "Mixed_7b" else "max_s1", x, c, 2)
+        conv(f"{n}.branch_pool", 2, y, 2048, 1856)
+        x = y
+    return out
+
+
+STEPS = steps()
+
+
+def block_writers():
+    """{Mixed block: the steps that write a branch into the block's concatenated rows, in program order}; the last is the block's last."""
+    out, cur = {}, None
+    for i, s in enumerate(STEPS):
+        if s["name"] and s["name"].startswith("Mixed"):
+            cur = s["name"].split(".")[0]
+        if cur and s["ldout"] != s["out_chw"][0]:
+            out.setdefault(cur, []).append(i)
+    return out
+
+
+def step_label(step):
+    s = STEPS[step]
+    return s["name"] if s["name"] else f"{s['kind']} after step {step - 1}"
+
+
+def _gamma(m):
+    return m * U32 / (1.0 - m * U32)
+
+
+def _fp16_rounding(ref):
+    """One rounding of a result to fp16: half an ulp, relative 2^-11 in the normal range, 2^-25 absolute below it."""
+    return 2.0 ** -11 * ref.abs() + 2.0 ** -25
+
+
+def exact_fold_bias(T, name):
+    """fl32(beta - mean) in T's dtype."""
+    return (T[f"{name}.bn.bias"].float() - T[f"{name}.bn.running_mean"].float()).to(T[f"{name}.bn.bias"].dtype)
+
+
+def step_apply(step, a, T, round_fn=None):
+    """One step in a's dtype on exact-fold parameters T (scale 1): the engine's stand-in when a is fp32 (round_fn = round_fp16 for the
+    fp16 engine). a: the step's input view (step 0: 8 channels, 3 of them used)."""
+    s = STEPS[step]
+    rf = round_fn if round_fn is not None else (lambda t: t)
+    if s["kind"] == "conv":
+        name, cin, _, _, stride, pad = CONV_BY_NAME[s["name"]]
+        return rf(F.relu(F.conv2d(a[:, :cin], T[f"{name}.conv.weight"], exact_fold_bias(T, name), stride=stride, padding=pad)))
+    if s["kind"] == "max_s2":
+        return F.max_pool2d(a, 3, 2)
+    if s["kind"] == "max_s1":
+        return F.max_pool2d(a, 3, 1, 1)
+    return rf(F.avg_pool2d(a, 3, 1, 1, count_include_pad=False))
+
+
+def step_reference(step, a, T, dtype="fp32"):
+    """(ref, tol) in fp64 of one step on the input view `a` as the engine held it. T: exact-fold parameters in fp64. dtype: the engine's
+    compute type. With u = 2^-24 and gamma(m) = m u / (1 - m u):
+      convolution   tol = gamma(K + 2) S + 1e-30, S = conv(|a|, |W|) + |b|, K = kh kw cinp: the worst case of an fp32-accumulated dot
+                    product of K terms in any order plus the bias; fp16 x fp16 products are exact in fp32, fp32 x fp16 ones round once
+                    (within gamma(K)); 1e-30 covers flushed denormal products (< 4032 terms below 2^-126); ReLU is 1-Lipschitz
+      average pool  tol = 10 u avg|a|: at most 8 additions and one division
+      max pools     tol = 0
+    fp16 adds the one rounding of the output."""
+    s = STEPS[step]
+    a = a.double()
+    if s["kind"] == "conv":
+        name, cin, _, (kh, kw), stride, pad = CONV_BY_NAME[s["name"]]
+        w, b = T[f"{name}.conv.weight"].double(), exact_fold_bias(T, name).double()
+        ref = F.relu(F.conv2d(a[:, :cin], w, b, stride=stride, padding=pad))
+        S = F.conv2d(a[:, :cin].abs(), w.abs(), b.abs(), stride=stride, padding=pad)
+        K = kh * kw * ((cin + 7) // 8 * 8)
+        tol = _gamma(K + 2) * S + 1e-30
+    elif s["kind"] == "avg_s1":
+        ref = F.avg_pool2d(a, 3, 1, 1, count_include_pad=False)
+        tol = 10 * U32 * F.avg_pool2d(a.abs(), 3, 1, 1, count_include_pad=False)
+    else:
+        ref = F.max_pool2d(a, 3, 2) if s["kind"] == "max_s2" else F.max_pool2d(a, 3, 1, 1)
+        return ref, torch.zeros_like(ref)
+    if dtype == "fp16":
+        tol = tol + _fp16_rounding(ref)
+    return ref, tol
+
+
+def gap_reference(a):
+    """(ref, tol) of the global average of the last step's output: 64 pixels added in fp32 and one division."""
+    a = a.double()
+    return a.mean(dim=(2, 3)), 65 * U32 * a.abs().mean(dim=(2, 3))
+
+
+def input_reference(x, dtype="fp32"):
+    """(ref, tol) in fp64, (n, 3, 299, 299), of the input kernel on x (n, 1 or 3, H, W) fp32 in [0, 1]: bilinear resize
+    (align_corners = False), 2 r - 1. Per pixel tol = 4 (ulp32(H) + ulp32(W)) D + 16 u: the source coordinate is formed in fp32 (the
+    scale H / 299, a product and a difference of magnitude <= H: within 2 ulp32(H), contracted into an fma or not), a coordinate error
+    d moves r by at most d D, D the largest difference among the pixel's four source neighbours, and 2 r - 1 doubles it; 16 u covers
+    the two lerps and the affine map on values in [-1, 1]. fp16 storage adds its one rounding."""
+    n, c, H, W = x.shape
+    xd = x.double()
+    if c == 1:
+        xd = xd.expand(-1, 3, -1, -1)
+    ref = 2 * F.interpolate(xd, size=(299, 299), mode="bilinear", align_corners=False) - 1
+
+    def cells(size):
+        f = np.maximum(size / 299.0 * (np.arange(299) + 0.5) - 0.5, 0.0)
+        i0 = np.minimum(np.floor(f).astype(np.int64), size - 1)
+        return torch.from_numpy(i0), torch.from_numpy(np.minimum(i0 + 1, size - 1))
+    y0, y1 = cells(H)
+    x0, x1 = cells(W)
+    nb = torch.stack([xd[:, :, yy][:, :, :, xx] for yy in (y0, y1) for xx in (x0, x1)])
+    D = nb.max(dim=0).values - nb.min(dim=0).values
+    tol = 4 * (float(np.spacing(np.float32(H))) + float(np.spacing(np.float32(W)))) * D + 16 * U32
+    if dtype == "fp16":
+        tol = tol + _fp16_rounding(ref)
+    return ref, tol
+
+
+def run_program(T, x, round_fn=None, hook=None, keep=False):
+    """The stand-in engine: the 107 steps in fp32 over the four buffers, as the device routes them. x: (n, 1 or 3, H, W) fp32.
+    hook(step, a, out) may return a replacement for a step's output (fault injection). Returns (features, records), records (if keep)
+    a list of (input view, output view) per step."""
+    rf = round_fn if round_fn is not None else (lambda t: t)
+    n = x.shape[0]
+    x3 = x.expand(-1, 3, -1, -1) if x.shape[1] == 1 else x
+    a = rf(2 * F.interpolate(x3, size=(299, 299), mode="bilinear", align_corners=False) - 1)
+    buf = {-1: torch.cat([a, torch.zeros(n, 5, 299, 299, dtype=a.dtype)], 1)}
+    rec = []
+    for i, s in enumerate(STEPS):
+        src = buf[s["src"]][:, :s["in_chw"][0]]
+        out = step_apply(i, src, T, round_fn)
+        if hook is not None:
+            r = hook(i, src, out)
+            out = out if r is None else r
+        d = buf.get(s["dst"])
+        if d is None or tuple(d.shape[1:]) != (s["ldout"],) + tuple(s["out_chw"][1:]):
+            d = buf[s["dst"]] = torch.zeros(n, s["ldout"], *s["out_chw"][1:], dtype=a.dtype)
+        d[:, s["coffout"]:s["coffout"] + s["out_chw"][0]] = out
+        if keep:
+            rec.append((src.clone(), out.clone()))
+    last = buf[STEPS[-1]["dst"]]
+    return last.mean(dim=(2, 3)), rec
+
+
+def worst_ratio(got, ref, tol):
+    """(largest error / tol, its index): 0 where the error is 0 (also at tol = 0), inf where tol = 0 is missed or got is not finite."""
+    err = (got.double() - ref).abs()
+    r = torch.where(err == 0, torch.zeros_like(err), err / tol)
+    r = torch.where(torch.isfinite(got.double()) & ~torch.isnan(r), r, torch.full_like(r, float("inf")))
+    j = int(r.argmax())
+    return float(r.reshape(-1)[j]), tuple(int(v) for v in np.unravel_index(j, r.shape))

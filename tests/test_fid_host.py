@@ -147,12 +147,46 @@ def test_new_symbols_are_declared_and_prototyped():
     names = ["gi_inception_create", "gi_inception_destroy", "gi_inception_param_floats", "gi_inception_workspace_bytes",
              "gi_inception_num_tensors", "gi_inception_tensor_desc", "gi_inception_bind", "gi_inception_sync_weights",
              "gi_inception_features", "gi_inception_debug_forward_convs", "gi_fid_stats_acc_doubles", "gi_fid_stats_update",
-             "gi_fid_stats_finish"]
+             "gi_fid_stats_finish", "gi_inception_num_steps", "gi_inception_step_desc", "gi_inception_debug_forward_steps",
+             "gi_inception_debug_read"]
     for n in names:
         assert re.search(r"\b%s\s*\(" % n, txt), n
         assert n in B.PROTOTYPES and hasattr(B.lib(), n), n
     assert B.lib().gi_fid_stats_acc_doubles(2048) == 1 + 2048 + 2048 * 2048
     assert "inception.hip" in open(os.path.join(ROOT, "gan-inpainting_amd", "csrc", "build.sh")).read()
+
+
+def test_step_inventory_equals_the_restated_program():
+    """The library's 107-step program (context-free handle) against tests/inception_ref.steps(), entry by entry."""
+    inception, _ = _fid()
+    import gan_inpainting_amd  # noqa: F401
+    from gan_inpainting_amd import backend as B
+    lib = B.lib()
+    prog = inception.InceptionV3.program()
+    assert len(prog) == len(R.STEPS) == 107
+    for i, (got, want) in enumerate(zip(prog, R.STEPS)):
+        assert got == {k: want[k] for k in got}, (i, got, want)
+        assert set(got) == {"kind", "conv", "in_chw", "out_chw", "src", "dst", "ldout", "coffout"}
+    assert [R.CONVS[p["conv"]][0] for p in prog if p["kind"] == "conv"] == [c[0] for c in R.CONVS]
+    h = C.c_void_p()
+    B.check(lib.gi_inception_create(None, B.GI_F16, 2, C.byref(h)))
+    try:
+        assert lib.gi_inception_num_steps(h) == 107 and lib.gi_inception_num_steps(None) == -1
+        five = (C.c_int * 5)()
+        p = C.cast(five, C.c_void_p)
+        for bad in (-1, 107):
+            with pytest.raises(B.BackendError):
+                B.check(lib.gi_inception_step_desc(h, bad, p, p, p, p, p))
+        with pytest.raises(B.BackendError):
+            B.check(lib.gi_inception_step_desc(h, 0, p, p, None, p, p))
+        # the debug entries compute: refused on a context-free handle, on the host
+        buf = (C.c_float * 16)()
+        with pytest.raises(B.BackendError):
+            B.check(lib.gi_inception_debug_forward_steps(h, C.cast(buf, C.c_void_p), 1, 1, 2, 2, 0))
+        with pytest.raises(B.BackendError):
+            B.check(lib.gi_inception_debug_read(h, 0, 0, 1, C.cast(buf, C.c_void_p)))
+    finally:
+        lib.gi_inception_destroy(h)
 
 
 def test_train_flag_defaults_off():
