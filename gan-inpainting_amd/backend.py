@@ -96,6 +96,10 @@ PROTOTYPES = {
     "gi_vgg19_sync_weights": (_i, [_vp]),
     "gi_vgg19_perceptual_style": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp]),
     "gi_vgg19_features": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gi_vgg19_grad_workspace_bytes": (_i64, [_vp]),
+    "gi_vgg19_bind_grad": (_i, [_vp, _vp, _i64]),
+    "gi_vgg19_perceptual_style_grad": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _f]),
+    "gi_vgg19_grad_layer": (_i, [_vp, _i, _vp]),
     "gi_inception_create": (_i, [_vp, _i, _i, _vp]),
     "gi_inception_destroy": (None, [_vp]),
     "gi_inception_param_floats": (_i64, [_vp]),

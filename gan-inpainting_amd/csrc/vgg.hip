@@ -2,8 +2,11 @@
 // (lib/models/loss.py:50-115 perceptual_loss / style_loss / perceptual_and_style_loss, gram_matrix
 // :117-136; taps after features[1,6,11,20,29] = relu1_1 .. relu5_1).
 //
-// Forward only: the reference evaluates these losses under no_grad on detached inputs, so nothing
-// reaches the generator. `output` and `target` run as ONE stacked batch of 2n images (NHWC fp16):
+// Forward: the reference evaluates these losses under no_grad on detached inputs, so by default nothing
+// reaches the generator and gi_vgg19_perceptual_style is all that runs. The opt-in backward (second half of
+// this file, gi_vgg19_perceptual_style_grad) is the analytic gradient of the same two terms
+// w.r.t. `output`: it needs its own workspace (gi_vgg19_bind_grad) and departs from the reference.
+// `output` and `target` run as ONE stacked batch of 2n images (NHWC fp16):
 //   conv1_1  the input is the grey image repeated over 3 channels (loss.py:54-55), so the 3->64 conv is
 //            a 1->64 conv with the weights summed over the input channel: one HBM-bound VALU kernel;
 //   12 more  3x3/s1/p1 convolutions + bias + ReLU: igemm3 mode 2 (fp16 MFMA implicit GEMM, LDS-DMA ring);
@@ -343,6 +346,298 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_f32_kernel(const half_t* __r
   }
 }
 
+
+// ================================================================================================================================
+// Opt-in backward: d(weight_p * P + weight_s * S) / d(output), target constant. Everything runs on s * gradient in fp16 with
+// fp32 accumulation, s = 2^k chosen on the device from the largest seed (vgg_scale_kernel) and removed in fp32 by the last kernel.
+// No float atomics: the only atomic is an unsigned max over bit patterns of non-negative floats, whose result does not depend on order.
+// ================================================================================================================================
+
+// [cout][cin][3][3] fp32 -> fp16 [cin][tap'][cout] with tap' = 8 - tap: the transpose of a 3x3 / s1 / p1 convolution is that convolution
+// with the taps reversed and the channel roles exchanged, so the input-gradient GEMMs run on the forward's mode-2 kernels
+__global__ void __launch_bounds__(256) pack3x3_t_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
+  const int64_t total = (int64_t)cin * 9 * cout;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int o = (int)(i % cout);
+    const int t = (int)((i / cout) % 9);
+    const int c = (int)(i / ((int64_t)cout * 9));
+    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + (8 - t)];
+  }
+}
+
+// max over a 256-thread workgroup, then ONE unsigned atomic max per workgroup (bit patterns of non-negative floats order like the
+// floats; a maximum does not depend on the order of its operands, so the result is the same in every run)
+__device__ __forceinline__ void amax_commit_block(float m, float* red4, unsigned* dst) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = fmaxf(fmaxf(red4[0], red4[1]), fmaxf(red4[2], red4[3]));
+    if (m > 0.f) atomicMax(dst, __float_as_uint(m));
+  }
+}
+
+// dense Gram difference of a tap from gram2_kernel's partial tiles: dg[pair][c1][c2] = (sum_s P_o - sum_s P_t) * scale, splits added in
+// ascending order (eight loads in flight), off-diagonal tiles mirrored (the matrix is symmetric); amax: max |dg| of the tap. A workgroup
+// owns a 16 x 16 block of a tile (grid: blocks per tile, tiles, pairs): both the block and its mirror image (through LDS) leave in 64-byte rows.
+__global__ void __launch_bounds__(256) gram_delta_kernel(const float* __restrict__ P, int nblk, int ntile, int split, int BLK, int C, float scale,
+                                                         float* __restrict__ dg, unsigned* __restrict__ amax) {
+  __shared__ float sm[16][17];
+  __shared__ float red[4];
+  const int bb = BLK * BLK, per_row = BLK / 16;
+  const int pair = blockIdx.z, tile = blockIdx.y;
+  const int r0 = (blockIdx.x / per_row) * 16, c0 = (blockIdx.x % per_row) * 16;
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const int e = (r0 + ty) * BLK + c0 + tx;
+  const float* po = P + ((((int64_t)pair * 2 + 0) * ntile + tile) * split) * bb + e;
+  const float* pt = P + ((((int64_t)pair * 2 + 1) * ntile + tile) * split) * bb + e;
+  float go = 0.f, gt = 0.f;
+  int k = 0;
+  for (; k + 8 <= split; k += 8) {
+    float vo[8], vt[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { vo[j] = po[(int64_t)(k + j) * bb]; vt[j] = pt[(int64_t)(k + j) * bb]; }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { go += vo[j]; gt += vt[j]; }
+  }
+  for (; k < split; ++k) { go += po[(int64_t)k * bb]; gt += pt[(int64_t)k * bb]; }
+  const float d = go * scale - gt * scale;
+  int t = tile, bi = 0;
+  for (; t >= nblk - bi; ++bi) t -= nblk - bi;
+  const int bj = bi + t;
+  float* D = dg + (int64_t)pair * C * C;
+  D[(int64_t)(bi * BLK + r0 + ty) * C + bj * BLK + c0 + tx] = d;
+  if (bi != bj) {
+    sm[ty][tx] = d;
+    __syncthreads();
+    D[(int64_t)(bj * BLK + c0 + ty) * C + bi * BLK + r0 + tx] = sm[tx][ty];
+  }
+  amax_commit_block(fabsf(d), red, amax);
+}
+
+// Seed of a tap: seed[p][c] = cs * sum_k dG[c][k] F_o[p][k] + cp * (F_o[p][c] - F_t[p][c])   (style: one MFMA GEMM per image, K = C;
+// perceptual: the epilogue). dG is rounded to fp16 after a power-of-two normalisation by its own maximum (dmax), which the fp32
+// coefficient takes back. A wave owns 64 pixels x 64 channels; both operands come straight from global memory in MFMA layout (dG is
+// symmetric: row c of dG is column c, K contiguous; F_o is pixel-major, K contiguous). The channel order per 16-row tile is
+// vgg_conv1_mfma_kernel's: a lane ends up with 2 x 8 consecutive channels of a pixel, 16-byte accesses.
+// STORE = true: s * seed in fp16 OVER the target half of the tap's feature map (each element of F_t is read by the one lane that
+// overwrites it; nothing else reads F_t after the forward).
+// STORE = false: max |seed| only - the magnitude the scale s is chosen from. Maps of more than kSeedSampleAll pixel blocks per image
+// are SAMPLED: one block of every eight (block 8 j + (3 j mod 8): all column positions, spread over the rows), so that this pass
+// costs an eighth of the store pass where the maps are large. The sample can only under-estimate the maximum; the headroom of
+// kSeedExp covers that.
+struct SeedP {
+  const half_t* Fo; half_t* Ft; const float* dg; const unsigned* dmax; unsigned* smax; const float* sc;
+  int C, HW, nb; float cp, cs;      // nb: 256-pixel blocks per image
+};
+constexpr int kSeedSampleAll = 8;
+template <bool STORE>
+__global__ void __launch_bounds__(256) vgg_seed_kernel(SeedP p) {
+  constexpr int NJ = 4;
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, g = lane >> 4;
+  int pb = blockIdx.x;
+  if (!STORE && p.nb > kSeedSampleAll) { pb = 8 * blockIdx.x + ((3 * blockIdx.x) & 7); if (pb >= p.nb) pb = 8 * blockIdx.x; }
+  const int pair = blockIdx.z, c0 = blockIdx.y * 64, pix0 = pb * 256 + wave * 64;
+  const half_t* Fo = p.Fo + (int64_t)pair * p.HW * p.C;
+  half_t* Ft = p.Ft + (int64_t)pair * p.HW * p.C;
+  const float* dg = p.dg + (int64_t)pair * p.C * p.C;
+  const float dm = __uint_as_float(*p.dmax);
+  int ex = 0;
+  if (dm > 0.f) (void)frexpf(dm, &ex);          // dm = m * 2^ex, m in [0.5, 1)
+  const float t = ldexpf(1.f, -ex), cs = p.cs * ldexpf(1.f, ex);
+  f4_t acc[4][NJ];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[mt][j] = f4_t{0.f, 0.f, 0.f, 0.f};
+  const float* arow[4];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) arow[mt] = dg + (int64_t)(c0 + ((mt >> 1) & 1) * 32 + (lr >> 2) * 8 + (mt & 1) * 4 + (lr & 3)) * p.C + g * 8;
+  bool ok[NJ];
+  const half_t* brow[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int pix = pix0 + 16 * j + lr;
+    ok[j] = pix < p.HW;
+    brow[j] = Fo + (int64_t)(ok[j] ? pix : 0) * p.C + g * 8;
+  }
+  for (int k0 = 0; k0 < p.C; k0 += 32) {
+    h8_t af[4], bf[NJ];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const f4_t x = *(const f4_t*)(arow[mt] + k0), y = *(const f4_t*)(arow[mt] + k0 + 4);
+      af[mt] = h8_t{(half_t)(x[0] * t), (half_t)(x[1] * t), (half_t)(x[2] * t), (half_t)(x[3] * t),
+                    (half_t)(y[0] * t), (half_t)(y[1] * t), (half_t)(y[2] * t), (half_t)(y[3] * t)};
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const u4_t raw = *(const u4_t*)(brow[j] + k0);
+      bf[j] = __builtin_bit_cast(h8_t, ok[j] ? raw : u4_t{0u, 0u, 0u, 0u});
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bf[j], acc[mt][j], 0, 0, 0);
+  }
+  // D row 4 g + r of tile mt is channel c0 + (mt >> 1) * 32 + g * 8 + (mt & 1) * 4 + r, D column lr is the pixel
+  const float s = STORE ? p.sc[0] : 1.f;
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (!ok[j]) continue;
+    const int64_t base = (int64_t)(pix0 + 16 * j + lr) * p.C + c0 + g * 8;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const h8_t fo = *(const h8_t*)(Fo + base + hf * 32), ft = *(const h8_t*)(Ft + base + hf * 32);
+      h8_t o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float val = fmaf(cs, acc[hf * 2 + (e >> 2)][j][e & 3], p.cp * ((float)fo[e] - (float)ft[e]));
+        if (STORE) o[e] = (half_t)(val * s);
+        else m = fmaxf(m, fabsf(val));
+      }
+      if (STORE) *(h8_t*)(Ft + base + hf * 32) = o;
+    }
+  }
+  if (!STORE) amax_commit_block(m, red, p.smax);
+}
+// s = 2^(kSeedExp - e) with max |seed| = m * 2^e, m in [0.5, 1): the largest seed lands in [2^(kSeedExp-1), 2^kSeedExp). All seeds zero
+// (output == target) or a non-finite maximum: s = 1. kSeedExp = -2: with the stand-in weights the largest gradient of
+// any layer stays within 2x the largest seed (fp64 oracle, 64x64 and 48x80), so 2^-2 leaves a factor 2^18 up to fp16's 65504 for
+// weights that amplify more, and 12 binades of normal numbers (22 with subnormals) below the maximum.
+constexpr int kSeedExp = -2;
+__global__ void vgg_scale_kernel(const unsigned* __restrict__ smax, float* __restrict__ sc) {
+  const float am = __uint_as_float(*smax);
+  int ex = 0;
+  float s = 1.f;
+  if (am > 0.f && am < INFINITY) {
+    (void)frexpf(am, &ex);
+    int k = kSeedExp - ex;
+    k = k > 100 ? 100 : (k < -100 ? -100 : k);
+    s = ldexpf(1.f, k);
+  }
+  sc[0] = s;
+  sc[1] = 1.f / s;
+}
+
+// Fused activation backward between two input-gradient GEMMs, 16-byte NHWC accesses, 8 channels per thread:
+//   POOL = false: out = [act > 0] * (g + seed)                     (g and / or seed may be null; out may alias g)
+//   POOL = true:  g lives on the (H/2, W/2) grid: every 2x2 window of `act` routes its value to the first maximum in row-major
+//                 order (F.max_pool2d's backward), times [act > 0]; the other three positions are written as zeros
+// relu = 0 drops the [act > 0] factor: the gradient w.r.t. the post-ReLU map itself (gi_vgg19_grad_layer).
+template <bool POOL>
+__global__ void __launch_bounds__(256) vgg_act_bwd_kernel(const half_t* g, const half_t* __restrict__ act, const half_t* __restrict__ seed,
+                                                          half_t* out, int nimg, int H, int W, int C, int relu) {
+  const int cg = C / 8;
+  const h8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (!POOL) {
+    const int64_t total = (int64_t)nimg * H * W * cg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+      const h8_t a = *(const h8_t*)(act + i * 8);
+      const h8_t gv = g ? *(const h8_t*)(g + i * 8) : z8;
+      const h8_t sv = seed ? *(const h8_t*)(seed + i * 8) : z8;
+      h8_t o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (!relu || (float)a[e] > 0.f) ? (half_t)((float)gv[e] + (float)sv[e]) : (half_t)0.f;
+      *(h8_t*)(out + i * 8) = o;
+    }
+  } else {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t total = (int64_t)nimg * Ho * Wo * cg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+      const int gq = (int)(i % cg);
+      const int64_t pq = i / cg;
+      const int x = (int)(pq % Wo);
+      const int64_t tt = pq / Wo;
+      const int y = (int)(tt % Ho);
+      const int64_t img = tt / Ho;
+      const int64_t o00 = (((img * H + 2 * y) * W + 2 * x) * (int64_t)C) + gq * 8;
+      const int64_t off[4] = {o00, o00 + C, o00 + (int64_t)W * C, o00 + (int64_t)W * C + C};
+      h8_t a[4], o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[q] = *(const h8_t*)(act + off[q]);
+      const h8_t gv = *(const h8_t*)(g + pq * C + gq * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        int best = 0;
+        float bv = (float)a[0][e];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) { const float av = (float)a[q][e]; if (av > bv) { bv = av; best = q; } }
+        const half_t val = (!relu || bv > 0.f) ? gv[e] : (half_t)0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q][e] = q == best ? val : (half_t)0.f;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *(h8_t*)(out + off[q]) = o[q];
+    }
+  }
+}
+
+// conv1_1 adjoint: dimg[n][y][x] = mul * sum_{ky,kx,o} w1[o][ky][kx] * D[n][y+1-ky][x+1-kx][o] (the grey image feeds all three input
+// channels, so the weights are sum_cin_kernel's w1, in fp32), mul = gscale / s with s from device memory: the fp16 scale leaves here.
+// A workgroup owns a 16 x 32 pixel tile: its threads reduce the 64 channels of each of the 18 x 34 halo pixels of D to nine per-tap
+// sums T[tap] (one pass over D: 128 bytes per pixel in 16-byte loads, the weights through wave-uniform addresses) into LDS, then
+// every output pixel adds its nine neighbours' sums. HBM-bound: D is read once plus the halo (20 %, mostly from L2).
+__global__ void __launch_bounds__(256) vgg_conv1_adjoint_kernel(const half_t* __restrict__ D, const float* __restrict__ w1, const float* __restrict__ sc,
+                                                                float gscale, float* __restrict__ dimg, int H, int W) {
+  constexpr int TH = 16, TW = 32, HH = TH + 2, HW_ = TW + 2, NH = HH * HW_;
+  __shared__ float T[NH * 9];
+  const int img = blockIdx.z, y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
+  const half_t* Di = D + (int64_t)img * H * W * 64;
+  for (int h = threadIdx.x; h < NH; h += 256) {
+    const int hy = h / HW_, hx = h - hy * HW_;
+    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
+    float t[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t[k] = 0.f;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      const half_t* src = Di + ((int64_t)y * W + x) * 64;
+      h8_t v[8];
+#pragma unroll
+      for (int c8 = 0; c8 < 8; ++c8) v[c8] = *(const h8_t*)(src + c8 * 8);
+#pragma unroll
+      for (int c8 = 0; c8 < 8; ++c8)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = (float)v[c8][e];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) t[k] = fmaf(w1[(c8 * 8 + e) * 9 + k], d, t[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) T[h * 9 + k] = t[k];
+  }
+  __syncthreads();
+  const float mul = gscale * sc[1];
+  for (int o = threadIdx.x; o < TH * TW; o += 256) {
+    const int ty = o / TW, tx = o - ty * TW;
+    const int y = y0 + ty, x = x0 + tx;
+    if (y >= H || x >= W) continue;
+    float s = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) s += T[((ty + 2 - ky) * HW_ + (tx + 2 - kx)) * 9 + ky * 3 + kx];
+    dimg[((int64_t)img * H + y) * W + x] = s * mul;
+  }
+}
+// NHWC fp16 (s * gradient) -> NCHW fp32 gradient (gi_vgg19_grad_layer)
+__global__ void __launch_bounds__(256) nhwc_to_nchw_unscale_kernel(const half_t* __restrict__ in, const float* __restrict__ sc, float* __restrict__ out,
+                                                                   int nimg, int HW, int C) {
+  const int64_t total = (int64_t)nimg * HW * C;
+  const float inv = sc[1];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const int64_t t = i / HW;
+    const int c = (int)(t % C);
+    const int64_t img = t / C;
+    out[i] = (float)in[(img * HW + p) * C + c] * inv;
+  }
+}
+
 int nblk(int64_t work, int per, int cap) {
   int64_t b = (work + per - 1) / per;
   if (b > cap) b = cap;
@@ -370,9 +665,65 @@ struct gi_vgg {
   VggFinP fin;            // per term: partial count and 1 / element count (filled by vgg_run)
   float* per_tap;         // 10 floats
   bool bound, synced;
+  // opt-in backward (gi_vgg19_bind_grad): a separate workspace; a handle that never binds it runs exactly as before
+  char* gws;
+  int64_t gws_bytes;
+  bool gbound;
+  int grad_n;             // pairs of the last grad call (0: none yet): gi_vgg19_grad_layer replays its backward
+  half_t* ga[NCONV];      // post-ReLU maps, [output half | target half]; the target half survives only at the taps
+  half_t* gpool[NCONV];   // 2x2 max pool of the pooled layers (both halves): the next layer's input
+  half_t* wT[NCONV];      // [1..12] fp16 weights of the transposed convolutions: [cin][reversed tap][cout]
+  half_t* gbuf[2];        // gradient ping-pong (n images)
+  float* dgram[5];        // per tap: dense G_o - G_t, [pairs][C][C] fp32
+  unsigned* amax;         // [0..4] max |G_o - G_t| per tap, [5] max |seed| over the taps (bit patterns of non-negative floats)
+  float* sc;              // [0] = s = 2^k, [1] = 1 / s: the backward runs on s * gradient
 };
 
 namespace {
+
+// grad workspace. The forward's maps go to two arenas, alternating per stage (convolution or pooling): a stage reads the other arena
+// and writes [output half | target half] behind what its arena must keep - the output halves of the 13 convolutions (ReLU masks,
+// pool routing) and both halves at the five taps - so a target half nobody needs is overwritten by the stage after next.
+int64_t vgg_gws_layout(gi_vgg* v, char* base) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
+  int64_t pos[2] = {0, 0}, ext[2] = {0, 0}, start[2 * NCONV];
+  int H = v->H, W = v->W, k = 0;
+  for (int i = 0; i < NCONV; ++i) {
+    const int64_t half = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
+    start[2 * i] = pos[k & 1];
+    if (start[2 * i] + 2 * half > ext[k & 1]) ext[k & 1] = start[2 * i] + 2 * half;
+    pos[k & 1] += half * (kTapAfter[i] >= 0 ? 2 : 1);
+    ++k;
+    start[2 * i + 1] = -1;
+    if (kPoolAfter[i]) {
+      H /= 2; W /= 2;
+      start[2 * i + 1] = pos[k & 1];       // kept by nobody: the next stage of this arena starts at the same place
+      const int64_t ph = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
+      if (start[2 * i + 1] + 2 * ph > ext[k & 1]) ext[k & 1] = start[2 * i + 1] + 2 * ph;
+      ++k;
+    }
+  }
+  char* arena[2];
+  arena[0] = take(ext[0]);
+  arena[1] = take(ext[1]);
+  for (int i = 0, kk = 0; i < NCONV; ++i) {
+    v->ga[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i]) : nullptr;
+    ++kk;
+    v->gpool[i] = nullptr;
+    if (kPoolAfter[i]) { v->gpool[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i + 1]) : nullptr; ++kk; }
+  }
+  v->wT[0] = nullptr;
+  for (int i = 1; i < NCONV; ++i) v->wT[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
+  const int64_t gbytes = (int64_t)v->max_pairs * v->H * v->W * 64 * 2;
+  v->gbuf[0] = (half_t*)take(gbytes);
+  v->gbuf[1] = (half_t*)take(gbytes);
+  const int tapC[5] = {64, 128, 256, 512, 512};
+  for (int t = 0; t < 5; ++t) v->dgram[t] = (float*)take((int64_t)v->max_pairs * tapC[t] * tapC[t] * 4);
+  v->amax = (unsigned*)take(256);
+  v->sc = (float*)take(256);
+  return off;
+}
 
 int64_t vgg_ws_layout(gi_vgg* v, char* base) {
   int64_t off = 0;
@@ -391,19 +742,23 @@ int64_t vgg_ws_layout(gi_vgg* v, char* base) {
   return off;
 }
 
-int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out) {
+// grad: every layer writes its own map in the grad workspace (nothing is overwritten that the backward reads), the pooled layers keep
+// their full-resolution map and pool in a separate pass, and every tap leaves its dense Gram difference behind
+int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out, bool grad = false) {
   hipStream_t st = v->ctx->stream;
   const int nimg = 2 * n;
   int H = v->H, W = v->W, cur = 0;
+  half_t* curp = grad ? v->ga[0] : v->act[0];
   // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of gi_vgg19_create)
   hipLaunchKernelGGL(vgg_conv1_mfma_kernel, dim3(nblk((int64_t)nimg * H * (W / 16), 4, 256 * 8)), dim3(256), 0, st, xa, xb, n, H, W, v->w1,
-                     v->params + v->boff[0], v->act[0]);
+                     v->params + v->boff[0], curp);
   GI_LAUNCH_CHECK();
   for (int i = 0; i < NCONV; ++i) {
     bool pooled = false;
     if (i > 0) {
       IgemmArgs a = {};
-      a.in = v->act[cur]; a.w = v->wpk[i]; a.out = v->act[cur ^ 1];
+      half_t* outp = grad ? v->ga[i] : v->act[cur ^ 1];
+      a.in = curp; a.w = v->wpk[i]; a.out = outp;
       a.bias = v->params + v->boff[i]; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
       a.n = nimg; a.Hs = H; a.Ws = W;
       a.cin = kCin[i]; a.ldin = kCin[i]; a.coffin = 0;
@@ -411,15 +766,16 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
       a.relu_in = 0; a.relu_cend = 0; a.act_out = GI_ACT_RELU; a.force_splitk = 0;
       // the pooled layers (conv1_2, conv2_2, conv3_4, conv4_4) are never taps: where the kernel can, it stores the 2x2 max pool of
       // its tile and the full-resolution map is never written
-      a.pool2 = (kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
+      a.pool2 = (!grad && kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
       GI_TRY(op_igemm3(st, 2, a));
       cur ^= 1;
+      curp = outp;
       pooled = a.pool_applied != 0;
     }
     const int C = kCout[i];
     const int tap = kTapAfter[i];
     if (tap >= 0) {
-      const half_t* F = v->act[cur];
+      const half_t* F = curp;
       const int64_t HW = (int64_t)H * W;
       if (feat_out && tap == stop_tap) {
         hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(nblk((int64_t)n * HW * C, 256, 4096)), dim3(256), 0, st, F, feat_out, n, (int)HW, C);
@@ -458,20 +814,111 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
         GI_LAUNCH_CHECK();
         v->fin.nb[5 + tap] = nb2;
         v->fin.inv[5 + tap] = 1.0 / (double)((int64_t)n * C * C);
+        if (grad) {
+          hipLaunchKernelGGL(gram_delta_kernel, dim3(BLK * BLK / 256, ntile, n), dim3(256), 0, st, (const float*)v->gram, nb_, ntile, split, BLK, C,
+                             (float)(1.0 / ((double)HW * C)), v->dgram[tap], v->amax + tap);
+          GI_LAUNCH_CHECK();
+        }
       }
     }
     if (kPoolAfter[i] && pooled) {
       H /= 2;
       W /= 2;
     } else if (kPoolAfter[i]) {
-      hipLaunchKernelGGL(maxpool2_kernel, dim3(nblk((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, v->act[cur],
-                         v->act[cur ^ 1], nimg, H / 2, W / 2, C);
+      hipLaunchKernelGGL(maxpool2_kernel, dim3(nblk((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, curp,
+                         grad ? v->gpool[i] : v->act[cur ^ 1], nimg, H / 2, W / 2, C);
       GI_LAUNCH_CHECK();
+      curp = grad ? v->gpool[i] : v->act[cur ^ 1];
       cur ^= 1;
       H /= 2;
       W /= 2;
     }
   }
+  return GI_OK;
+}
+
+int act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
+  if (pool) {
+    hipLaunchKernelGGL(vgg_act_bwd_kernel<true>, dim3(nblk((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H,
+                       W, C, relu);
+  } else {
+    hipLaunchKernelGGL(vgg_act_bwd_kernel<false>, dim3(nblk((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C, relu);
+  }
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+
+// seeds of the five taps from the maps and Gram differences the grad forward left: first their maximum, then s, then s * seed over F_t
+int vgg_seeds(gi_vgg* v, int n, float weight_p, float weight_s) {
+  hipStream_t st = v->ctx->stream;
+  for (int pass = 0; pass < 2; ++pass) {
+    int H = v->H, W = v->W;
+    for (int i = 0; i < NCONV; ++i) {
+      const int tap = kTapAfter[i], C = kCout[i];
+      if (tap >= 0) {
+        const int64_t HW = (int64_t)H * W;
+        SeedP p;
+        p.Fo = v->ga[i]; p.Ft = v->ga[i] + (int64_t)n * HW * C; p.dg = v->dgram[tap]; p.dmax = v->amax + tap; p.smax = v->amax + 5; p.sc = v->sc;
+        p.C = C; p.HW = (int)HW; p.nb = (int)((HW + 255) / 256);
+        p.cp = (float)((double)weight_p * 2.0 / ((double)n * C * HW));
+        p.cs = (float)((double)weight_s * 4.0 / ((double)n * C * C * (double)HW * C));
+        const int nbx = pass == 0 && p.nb > kSeedSampleAll ? (p.nb + 7) / 8 : p.nb;      // pass 0: large maps are sampled (vgg_seed_kernel)
+        const dim3 grid(nbx, C / 64, n);
+        if (pass == 0) hipLaunchKernelGGL(vgg_seed_kernel<false>, grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(vgg_seed_kernel<true>, grid, dim3(256), 0, st, p);
+        GI_LAUNCH_CHECK();
+      }
+      if (kPoolAfter[i]) { H /= 2; W /= 2; }
+    }
+    if (pass == 0) {
+      hipLaunchKernelGGL(vgg_scale_kernel, dim3(1), dim3(1), 0, st, (const unsigned*)(v->amax + 5), v->sc);
+      GI_LAUNCH_CHECK();
+    }
+  }
+  return GI_OK;
+}
+
+// The chain from conv5_1 down. D_l = s * gradient w.r.t. the PRE-activation of layer l = [a_l > 0] * (transposed conv of D_(l+1), un-pooled
+// where a pool sits between, + seed_l at a tap). stop < 0: down to D_0, then the conv1_1 adjoint into grad_out. stop = L: the gradient
+// w.r.t. the post-ReLU map of layer L (no [a_L > 0] factor) goes to layer_out as NCHW fp32, de-scaled.
+int vgg_backward(gi_vgg* v, int n, int stop, float* layer_out, float* grad_out, float gscale) {
+  hipStream_t st = v->ctx->stream;
+  int Hl[NCONV], Wl[NCONV];
+  { int H = v->H, W = v->W; for (int i = 0; i < NCONV; ++i) { Hl[i] = H; Wl[i] = W; if (kPoolAfter[i]) { H /= 2; W /= 2; } } }
+  auto seed_of = [&](int l) -> const half_t* { return kTapAfter[l] >= 0 ? v->ga[l] + (int64_t)n * Hl[l] * Wl[l] * kCout[l] : nullptr; };
+  auto readback = [&](const half_t* g, int l) -> int {
+    hipLaunchKernelGGL(nhwc_to_nchw_unscale_kernel, dim3(nblk((int64_t)n * Hl[l] * Wl[l] * kCout[l], 256, 4096)), dim3(256), 0, st, g, (const float*)v->sc,
+                       layer_out, n, Hl[l] * Wl[l], kCout[l]);
+    GI_LAUNCH_CHECK();
+    return GI_OK;
+  };
+  int cur = 0;
+  GI_TRY(act_bwd(st, false, nullptr, v->ga[NCONV - 1], seed_of(NCONV - 1), v->gbuf[cur], n, Hl[NCONV - 1], Wl[NCONV - 1], kCout[NCONV - 1], stop != NCONV - 1));
+  if (stop == NCONV - 1) return readback(v->gbuf[cur], NCONV - 1);
+  for (int l = NCONV - 1; l >= 1; --l) {
+    const int below = l - 1;
+    const bool pool = kPoolAfter[below] != 0, last = stop == below;
+    IgemmArgs a = {};
+    a.in = v->gbuf[cur]; a.w = v->wT[l]; a.out = v->gbuf[cur ^ 1];
+    a.n = n; a.Hs = Hl[l]; a.Ws = Wl[l];
+    a.cin = kCout[l]; a.ldin = kCout[l]; a.cout = kCin[l]; a.ldout = kCin[l];
+    a.act_out = GI_ACT_NONE;
+    if (!pool && !last) {     // the ReLU mask of the layer below (+ its seed) in the GEMM epilogue, where the dispatched kernel has one
+      a.mask = v->ga[below]; a.ldmask = kCin[l]; a.coffmask = 0; a.mask_slope = 0.f;
+      a.add = seed_of(below); a.ldadd = kCin[l]; a.coffadd = 0;
+    }
+    GI_TRY(op_igemm3(st, 2, a));
+    if (pool) {
+      GI_TRY(act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
+    } else {
+      cur ^= 1;
+      if (!a.mask || !a.mask_applied) GI_TRY(act_bwd(st, false, v->gbuf[cur], v->ga[below], seed_of(below), v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
+    }
+    if (last) return readback(v->gbuf[cur], below);
+  }
+  hipLaunchKernelGGL(vgg_conv1_adjoint_kernel, dim3((v->W + 31) / 32, (v->H + 15) / 16, n), dim3(256), 0, st, (const half_t*)v->gbuf[cur], (const float*)v->w1,
+                     (const float*)v->sc, gscale, grad_out, v->H, v->W);
+  GI_LAUNCH_CHECK();
   return GI_OK;
 }
 
@@ -495,6 +942,8 @@ int gi_vgg19_create(gi_ctx* ctx, int H, int W, int max_pairs, gi_vgg** out) {
   }
   v->param_floats = off;
   v->params = nullptr; v->ws = nullptr; v->bound = false; v->synced = false;
+  v->gws = nullptr; v->gbound = false; v->grad_n = 0;
+  v->gws_bytes = vgg_gws_layout(v, nullptr);
   v->ws_bytes = vgg_ws_layout(v, nullptr);
   *out = v;
   return GI_OK;
@@ -533,6 +982,13 @@ int gi_vgg19_sync_weights(gi_vgg* v) {
                        v->wpk[i], kCout[i], kCin[i]);
     GI_LAUNCH_CHECK();
   }
+  if (v->gbound) {     // the transposed convolutions' weights, only for a handle that can run the backward
+    for (int i = 1; i < NCONV; ++i) {
+      hipLaunchKernelGGL(pack3x3_t_kernel, dim3(nblk((int64_t)kCout[i] * 9 * kCin[i], 256, 2048)), dim3(256), 0, st, v->params + v->woff[i],
+                         v->wT[i], kCout[i], kCin[i]);
+      GI_LAUNCH_CHECK();
+    }
+  }
   v->synced = true;
   return GI_OK;
 }
@@ -545,6 +1001,46 @@ int gi_vgg19_perceptual_style(gi_vgg* v, const float* output, const float* targe
   hipLaunchKernelGGL(vgg_finish_kernel, dim3(1), dim3(256), 0, v->ctx->stream, (const double*)v->partial, v->fin, v->per_tap, weight_p, weight_s, out2);
   GI_LAUNCH_CHECK();
   if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, v->ctx->stream));
+  return GI_OK;
+}
+
+int64_t gi_vgg19_grad_workspace_bytes(const gi_vgg* v) { return v ? v->gws_bytes : -1; }
+
+int gi_vgg19_bind_grad(gi_vgg* v, void* ws, int64_t ws_bytes) {
+  GI_REQUIRE(v && ws, "vgg19_bind_grad: null argument");
+  GI_REQUIRE(v->bound, "vgg19_bind_grad: gi_vgg19_bind first");
+  GI_REQUIRE(ws_bytes >= v->gws_bytes && ((uintptr_t)ws & 255) == 0, "vgg19_bind_grad: workspace %lld bytes (need %lld, 256-byte aligned)",
+             (long long)ws_bytes, (long long)v->gws_bytes);
+  v->gws = (char*)ws;
+  vgg_gws_layout(v, v->gws);
+  v->gbound = true; v->synced = false; v->grad_n = 0;      // sync_weights packs the transposed weights
+  return GI_OK;
+}
+
+int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* target, int n, float weight_p, float weight_s, float* out2,
+                                   float* per_tap10, float* grad_out, float gscale) {
+  GI_REQUIRE(v && v->gbound, "vgg19_perceptual_style_grad: no grad workspace bound (gi_vgg19_bind_grad)");
+  GI_REQUIRE(v->bound && v->synced, "vgg19_perceptual_style_grad: bind + sync_weights first");
+  GI_REQUIRE(output && target && out2 && grad_out && n > 0 && n <= v->max_pairs, "vgg19_perceptual_style_grad: n=%d (max %d)", n, v->max_pairs);
+  hipStream_t st = v->ctx->stream;
+  v->grad_n = 0;
+  GI_HIP(hipMemsetAsync(v->amax, 0, 256, st));
+  GI_TRY(vgg_run(v, output, target, n, -1, nullptr, true));
+  hipLaunchKernelGGL(vgg_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)v->partial, v->fin, v->per_tap, weight_p, weight_s, out2);
+  GI_LAUNCH_CHECK();
+  if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  GI_TRY(vgg_seeds(v, n, weight_p, weight_s));
+  v->grad_n = n;
+  GI_TRY(vgg_backward(v, n, -1, nullptr, grad_out, gscale));
+  return GI_OK;
+}
+
+int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw) {
+  GI_REQUIRE(v && v->gbound, "vgg19_grad_layer: no grad workspace bound (gi_vgg19_bind_grad)");
+  GI_REQUIRE(v->synced && v->grad_n > 0, "vgg19_grad_layer: no gi_vgg19_perceptual_style_grad call to read back");
+  GI_REQUIRE(out_nchw && layer >= 0 && layer < NCONV, "vgg19_grad_layer: layer=%d", layer);
+  // replays the backward of the last grad call from what it left in the workspace (maps, seeds, scale), down to `layer`
+  GI_TRY(vgg_backward(v, v->grad_n, layer, out_nchw, nullptr, 1.f));
   return GI_OK;
 }
 

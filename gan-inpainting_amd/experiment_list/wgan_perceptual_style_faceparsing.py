@@ -8,7 +8,9 @@ variation (:206-222). Fixes forced by the file: one=+1 / mone=-1 (uninitialised 
 
 state['segmentation_model']: a gan_inpainting_amd UnetGenerator(1,4,7,ngf=32) (frozen, eval) or None (term
 dropped); state['vgg']: a networks.VGG19Wrapper, None = random-initialised stand-in (the pretrained torchvision
-download of networks.py:371 is not available here; load it with VGG19Wrapper.load_state_dict), False = terms dropped."""
+download of networks.py:371 is not available here; load it with VGG19Wrapper.load_state_dict), False = terms dropped.
+state['perceptual_grad'] (train.py --perceptual-grad, default off): the two VGG-19 terms reach the generator through their
+analytic gradient. The reference does not back-propagate them; a wrapper passed in state['vgg'] must then be built with grad=True."""
 from . import _common as C
 from ..lib.models import loss, networks
 
@@ -23,13 +25,19 @@ def begin(state, loaders):
     else:
         seg = seg.to(device)
     vgg = state.get("vgg")
+    pgrad = bool(state.get("perceptual_grad", False))
     if vgg is None:
-        logger.info("no VGG-19 weights in state['vgg']: random-initialised feature network (perceptual/style are logged constants)")
-        vgg = networks.VGG19Wrapper(max_pairs=state["batchsize"]).to(device)
+        logger.info("no VGG-19 weights in state['vgg']: random-initialised feature network (perceptual/style are %s)",
+                    "back-propagated" if pgrad else "logged constants")
+        vgg = networks.VGG19Wrapper(max_pairs=state["batchsize"], grad=pgrad).to(device)
     elif vgg is False:
         vgg = None
+    if pgrad and vgg is not None:
+        logger.info("perceptual_grad: the perceptual/style terms are back-propagated into the generator - this departs from the "
+                    "reference, which evaluates them under no_grad; the fp16 range of the published VGG-19 weights is unchecked")
+    pgrad = pgrad and vgg is not None
     step = C.trainer.WGANPerceptualStep(net_G, net_D, opt_G, opt_D, vgg=vgg, segment_model=seg, clip=0.01, sync=C.make_sync(),
-                                        overlap=bool(state.get("overlap", True)))
+                                        overlap=bool(state.get("overlap", True)), perceptual_grad=pgrad)
     counters = {"G_iter_count": 0}
 
     def batch(bi, ground, mask, segment):

@@ -153,18 +153,52 @@ def _vgg_for(x):
     return vgg
 
 
-def perceptual_and_style_loss(output, target, weight_p=0.05, weight_s=100):
-    """loss.py:93-115. Constants w.r.t. the generator, exactly like the reference (no_grad + detach)."""
+class _VggFn(torch.autograd.Function):
+    """(p, s) with d(p + s)/d(output) computed in the forward call (one VGG-19 forward + backward on the device). The kernels
+    back-propagate the SUM of both terms, so there is one image gradient for both results: backward multiplies it by the factor
+    of the term whose weight is not zero, or - with both weights set - by the mean of the two incoming factors, which is exact
+    whenever the two results enter the loss with the same factor (they do wherever they are added up)."""
+
+    @staticmethod
+    def forward(ctx, output, target, weight_p, weight_s, net):
+        p, s, grad = net.perceptual_and_style_grad(output, target, weight_p, weight_s)
+        ctx.grad = grad
+        ctx.which = "p" if weight_s == 0 else ("s" if weight_p == 0 else "both")
+        return p.clone(), s.clone()
+
+    @staticmethod
+    def backward(ctx, gp, gs):
+        g = gp if ctx.which == "p" else (gs if ctx.which == "s" else 0.5 * (gp + gs))
+        return ctx.grad * g, None, None, None, None
+
+
+def _vgg_grad_for(x):
+    net = _vgg_for(x)
+    if not getattr(net, "grad", False):
+        raise B.BackendError("differentiable=True needs a VGG19Wrapper built with grad=True (loss.set_vgg)")
+    return net
+
+
+def perceptual_and_style_loss(output, target, weight_p=0.05, weight_s=100, differentiable=False):
+    """loss.py:93-115. Constants w.r.t. the generator, exactly like the reference (no_grad + detach). differentiable=True (not in
+    the reference): with an `output` that requires grad the two scalars carry the analytic gradient w.r.t. `output`; they must be
+    added with equal factors (one image gradient serves their sum)."""
+    if differentiable and output.requires_grad:
+        return _VggFn.apply(output, target, weight_p, weight_s, _vgg_grad_for(output))
     return _vgg_for(output).perceptual_and_style(output, target, weight_p, weight_s)
 
 
-def perceptual_loss(output, target, weight=0.05):
+def perceptual_loss(output, target, weight=0.05, differentiable=False):
     """loss.py:50-69."""
+    if differentiable and output.requires_grad:
+        return _VggFn.apply(output, target, weight, 0.0, _vgg_grad_for(output))[0]
     return _vgg_for(output).perceptual_and_style(output, target, weight, 0.0)[0]
 
 
-def style_loss(output, target, weight=0.1):
+def style_loss(output, target, weight=0.1, differentiable=False):
     """loss.py:71-90."""
+    if differentiable and output.requires_grad:
+        return _VggFn.apply(output, target, 0.0, weight, _vgg_grad_for(output))[1]
     return _vgg_for(output).perceptual_and_style(output, target, 0.0, weight)[1]
 
 

@@ -797,7 +797,12 @@ class VGG19Wrapper(nn.Module):
     """The feature network behind the perceptual / style losses (reference networks.py:367-389:
     torchvision `vgg19(pretrained=True)` with hooks on features[1,6,11,20,29]; loss.py:4 builds one at
     import). Here: the 13 convolutions up to features.28 as one flat fp32 parameter buffer driven by
-    `gi_vgg19_*` (fp16 MFMA 3x3 implicit GEMM, forward only - the reference calls it under no_grad).
+    `gi_vgg19_*` (fp16 MFMA 3x3 implicit GEMM; the reference calls it under no_grad, and so does
+    `perceptual_and_style`).
+
+    `grad=True` additionally binds the backward's workspace (the kept feature maps: 2.36 GB at 512x512
+    with 8 pairs) and enables `perceptual_and_style_grad` / `grad_layer`: the analytic gradient of
+    the two terms w.r.t. `output`. That departs from the reference, which never back-propagates them.
 
     The pretrained weights cannot be downloaded in this environment: the constructor initialises like
     torchvision does for `pretrained=False` (He-normal fan_out, zero bias); `load_state_dict` accepts a
@@ -807,9 +812,10 @@ class VGG19Wrapper(nn.Module):
     CONV_IDX = (0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28)
     CHANNELS = (64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512)
 
-    def __init__(self, max_pairs=8):
+    def __init__(self, max_pairs=8, grad=False):
         super().__init__()
         self.max_pairs = max_pairs
+        self.grad = bool(grad)
         sizes, cin = [], 3
         for cout in self.CHANNELS:
             sizes.append((cout, cin))
@@ -862,6 +868,11 @@ class VGG19Wrapper(nn.Module):
             ws = torch.empty(lib.gi_vgg19_workspace_bytes(hd) + 256, dtype=torch.uint8, device=dev)
             off = (-ws.data_ptr()) % 256
             B.check(lib.gi_vgg19_bind(hd, B.ptr(self.flat), ws.data_ptr() + off, ws.numel() - off))
+            if self.grad:
+                gws = torch.empty(lib.gi_vgg19_grad_workspace_bytes(hd) + 256, dtype=torch.uint8, device=dev)
+                goff = (-gws.data_ptr()) % 256
+                B.check(lib.gi_vgg19_bind_grad(hd, gws.data_ptr() + goff, gws.numel() - goff))
+                ws = (ws, gws)
             self._handles[key] = (hd, ws)
             self._dirty = True
         hd = self._handles[key][0]
@@ -891,6 +902,33 @@ class VGG19Wrapper(nn.Module):
         B.check(B.lib().gi_vgg19_perceptual_style(hd, B.ptr(output), B.ptr(target), output.shape[0], float(weight_p), float(weight_s),
                                                   B.ptr(out), B.ptr(taps)))
         return (out[0], out[1], taps) if per_tap else (out[0], out[1])
+
+    @torch.no_grad()
+    def perceptual_and_style_grad(self, output, target, weight_p, weight_s, gscale=1.0):
+        """(p, s, grad): the two values of `perceptual_and_style` and gscale * d(p + s)/d(output), shaped like `output`
+        (`target` is a constant). Needs a wrapper built with grad=True."""
+        self._check(output)
+        self._check(target)
+        output, target = output.detach().contiguous(), target.detach().contiguous()
+        hd = self._handle(output.shape[2], output.shape[3], output.device)
+        out = torch.empty(2, dtype=torch.float32, device=output.device)
+        grad = torch.empty_like(output)
+        B.check(B.lib().gi_vgg19_perceptual_style_grad(hd, B.ptr(output), B.ptr(target), output.shape[0], float(weight_p), float(weight_s),
+                                                       B.ptr(out), None, B.ptr(grad), float(gscale)))
+        self._last = (hd, output.shape)
+        return out[0], out[1], grad
+
+    @torch.no_grad()
+    def grad_layer(self, layer):
+        """Gradient w.r.t. the post-ReLU map of convolution `layer` (0..12) from the last `perceptual_and_style_grad`
+        call as (n,C,h,w) float32 (parity checks; gscale not applied)."""
+        if getattr(self, "_last", None) is None:
+            raise B.BackendError("VGG19Wrapper.grad_layer: no perceptual_and_style_grad call to read back")
+        hd, (n, _, h, w) = self._last
+        s = 1 << sum(1 for i in (1, 3, 7, 11) if i < layer)
+        out = torch.empty(n, self.CHANNELS[layer], h // s, w // s, dtype=torch.float32, device=self.flat.device)
+        B.check(B.lib().gi_vgg19_grad_layer(hd, int(layer), B.ptr(out)))
+        return out
 
     @torch.no_grad()
     def features(self, x, tap):

@@ -57,7 +57,7 @@ def shard_rows(df, rank, world, batchsize):
     return df.iloc[:keep].iloc[rank::world].reset_index(drop=True)
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-exp", "--experiments", nargs="+", required=True)
     parser.add_argument("-ep", "--numepoch", type=int, default=1500)
@@ -87,7 +87,16 @@ def main(argv=None):
     parser.add_argument("--data", default="synthetic")
     parser.add_argument("--samples", type=int, default=1024)
     parser.add_argument("--outdir", default=os.path.join(os.getcwd(), "runs"))
-    args = parser.parse_args(argv)
+    parser.add_argument("--perceptual-grad", dest="perceptual_grad", action="store_true", default=False,
+                        help="wgan_perceptual_style_faceparsing: back-propagate the VGG-19 perceptual and style terms into the generator. "
+                             "This DEPARTS from the reference, which evaluates both under no_grad (they are logged constants there). "
+                             "Only the random stand-in feature network has been run: the fp16 range of the published weights' "
+                             "activations and gradients is unchecked")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     state = vars(args)
 
     import gan_inpainting_amd  # noqa: F401

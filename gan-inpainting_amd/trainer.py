@@ -471,12 +471,18 @@ class WGANPerceptualStep(WGANStep):
     no_grad), face_parsing = 0.01 * CrossEntropy(w=[0,1.2,0.7,0.7])(segment_model(inpainted), segment) (:212-213,
     frozen eval network: input gradient only), tv = tv_loss(inpainted, 1) (:219).
     `vgg` (networks.VGG19Wrapper) and `segment_model` (frozen UnetGenerator(1,4,7,ngf=32)) are optional: a missing
-    one drops its term (the pretrained weights of both are not redistributable / not available here)."""
+    one drops its term (the pretrained weights of both are not redistributable / not available here).
+    perceptual_grad=True (NOT the reference, which never back-propagates these two terms): their analytic image gradient
+    (VGG19Wrapper(grad=True).perceptual_and_style_grad) joins the other generator terms."""
 
     def __init__(self, net_G, net_D, opt_G, opt_D, vgg=None, segment_model=None, weight_p=0.01, weight_s=0.01, weight_fp=0.01,
-                 tv_weight=1.0, ce_weight=(0, 1.2, 0.7, 0.7), **kw):
+                 tv_weight=1.0, ce_weight=(0, 1.2, 0.7, 0.7), perceptual_grad=False, **kw):
         super().__init__(net_G, net_D, opt_G, opt_D, recon="rmse", **kw)
         self.recon_weight = 2.0
+        self.perceptual_grad = bool(perceptual_grad)
+        if self.perceptual_grad and not getattr(vgg, "grad", False):
+            raise B.BackendError("WGANPerceptualStep(perceptual_grad=True) needs vgg=VGG19Wrapper(..., grad=True)")
+        self._vgg_scaled_for = None
         self.vgg, self.weight_p, self.weight_s = vgg, weight_p, weight_s
         self.tv_weight, self.weight_fp, self.ce_weight = tv_weight, weight_fp, list(ce_weight)
         self.seg = getattr(segment_model, "phys", segment_model)      # EmbeddedUnetGenerator -> the physical network
@@ -500,7 +506,19 @@ class WGANPerceptualStep(WGANStep):
         o.add(self.g_rec, self.tmp2, self.g_rec)
         o.tv(inp, self.tv_weight, self._loss("tv"), self.tmp2)                                 # :219
         o.add(self.g_rec, self.tmp2, self.g_rec)
-        if self.vgg is not None:                                                               # :216 (no gradient)
+        if self.vgg is not None and self.perceptual_grad:
+            p, s, gv = self.vgg.perceptual_and_style_grad(inp, ground, self.weight_p, self.weight_s)
+            self.L["perceptual"], self.L["style"] = p.view(1), s.view(1)
+            if self.auto_loss_scale and self.G._dtype == B.GI_F16 and self._vgg_scaled_for != self._shape:
+                # the fp16 generator's loss scale assumes ~ recon_weight / (N H W) per pixel; how much these terms add depends on
+                # the feature network and the weights, not on the geometry: ONE host read at the first generator update of a batch
+                # geometry puts their largest per-pixel gradient, in the same units, on top of the two RMSE terms
+                n, _, h, w = inp.shape
+                self.recon_weight = 2.0 + float(gv.abs().max()) * n * h * w
+                self._pick_loss_scales(ground)
+                self._vgg_scaled_for = self._shape
+            o.add(self.g_rec, gv, self.g_rec)
+        elif self.vgg is not None:                                                             # :216 (no gradient)
             p, s = self.vgg.perceptual_and_style(inp, ground, self.weight_p, self.weight_s)
             self.L["perceptual"], self.L["style"] = p.view(1), s.view(1)
         if self.seg is not None and self.segment is not None:                                  # :212-213

@@ -356,7 +356,8 @@ int gi_loss_cross_entropy(gi_ctx* ctx, const float* logits, const int64_t* label
 
 /* VGG-19 features for perceptual_loss / style_loss / perceptual_and_style_loss (lib/models/loss.py:50-115)
  * and gram_matrix (:117-136): taps relu1_1, relu2_1, relu3_1, relu4_1, relu5_1 (features[1,6,11,20,29]) of
- * the grey image repeated over 3 channels (:54-55). Forward only (the reference runs it under no_grad).
+ * the grey image repeated over 3 channels (:54-55). The reference runs it under no_grad; the backward below is
+ * opt-in and needs a workspace of its own.
  * params: fp32, torchvision layout, the 13 convolutions up to features.28 (gi_vgg19_tensor_desc gives
  * name "features.<i>.weight|bias", shape, offset); fp16 MFMA compute. max_pairs = largest n. */
 typedef struct gi_vgg gi_vgg;
@@ -374,6 +375,20 @@ int gi_vgg19_perceptual_style(gi_vgg* v, const float* output, const float* targe
                               float weight_s, float* out2, float* per_tap10);
 /* feature map of tap 0..4 as (n,C,h,w) fp32 (parity checks) */
 int gi_vgg19_features(gi_vgg* v, const float* x, int n, int tap, float* out_nchw);
+/* Opt-in backward of the two terms w.r.t. `output` (target is a constant; the reference never back-propagates them).
+ * It keeps the forward's feature maps in a separate workspace: query, bind after gi_vgg19_bind (256-byte aligned), then
+ * gi_vgg19_sync_weights. A handle that never binds it allocates and runs exactly as without these entries; every entry
+ * below fails with GI_ERR_INVALID on such a handle.
+ * gi_vgg19_perceptual_style_grad: out2 / per_tap10 as gi_vgg19_perceptual_style (same kernels, same values);
+ * grad_out: n*H*W floats = gscale * d(out2[0] + out2[1]) / d(output). fp16 with fp32 accumulation at a power-of-two scale
+ * chosen on the device; bit-reproducible (no float atomics).
+ * gi_vgg19_grad_layer (parity / debugging): the gradient w.r.t. the post-ReLU map of convolution `layer` (0..12) of the
+ * last grad call as (n,C,h,w) fp32, gscale not applied; replays that call's backward from the workspace. */
+int64_t gi_vgg19_grad_workspace_bytes(const gi_vgg* v);
+int gi_vgg19_bind_grad(gi_vgg* v, void* ws, int64_t ws_bytes);
+int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* target, int n, float weight_p,
+                                   float weight_s, float* out2, float* per_tap10, float* grad_out, float gscale);
+int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw_f32);
 
 /* ---- Frechet Inception Distance (reference lib/fid/): Inception-V3 pool3 features + streaming statistics ----
  * The FID variant of Inception-V3 (lib/fid/inception.py: average pools that do not count padding in Mixed_5b..5d,
