@@ -132,6 +132,13 @@ PROTOTYPES = {
     "gi_rmsprop_step_scan": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _i]),
     "gi_wgrad_s2_scratch_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "gi_wgrad_s2_ws": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64]),
+    "gi_c1_gather": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "gi_c1_scatter": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
+    "gi_c1_wgrad": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _i64]),
+    "gi_c1_wgrad_reduce": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i64]),
+    "gi_c1_head4_col_bytes": (_i64, [_i, _i, _i]),
+    "gi_c1_head4_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "gi_c1_head4_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "gi_conv_s2_forward": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
     "gi_convT_s2_forward": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64]),
     "gi_wgrad_s2": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f]),

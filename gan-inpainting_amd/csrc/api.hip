@@ -235,6 +235,54 @@ int gi_wgrad_s2_ws(gi_ctx* ctx, int dtype, const void* S, const void* L, float* 
 }
 
 
+// ---- the single-channel layers (c1.hip) on their own: what tests/test_c1_gpu.py drives ------------------------------------------
+int gi_c1_gather(gi_ctx* ctx, int dtype, const float* img, const float* w, void* out, int n, int Hs, int Ws, int c, int ldout, int coffout,
+                 int act_out, float in_scale, const float* bias, unsigned long long* bits, int* bits_written) {
+  GI_REQUIRE(ctx && img && w && out, "c1_gather: null pointer");
+  return op_c1_gather(ctx->stream, dtype, img, w, out, n, Hs, Ws, c, ldout, coffout, act_out, in_scale, bias, bits, bits_written);
+}
+
+int gi_c1_scatter(gi_ctx* ctx, int dtype, const void* X, const float* w, const float* bias, float* img, int n, int Hs, int Ws, int c, int ldx,
+                  int coffx, int relu_in, int post, float out_scale, void* col_scratch, float* img2, const void* x2, int ld2,
+                  const float* scale2, const float* shift2) {
+  GI_REQUIRE(ctx && X && w && img, "c1_scatter: null pointer");
+  GI_REQUIRE(!x2 || (scale2 && shift2), "c1_scatter: x2 without scale2 / shift2");
+  C1Affine aff;
+  aff.x2 = x2; aff.ld2 = ld2; aff.scale = scale2; aff.shift = shift2;
+  return op_c1_scatter(ctx->stream, dtype, X, w, bias, img, n, Hs, Ws, c, ldx, coffx, relu_in, post, out_scale, col_scratch, img2,
+                       x2 ? &aff : nullptr);
+}
+
+int gi_c1_wgrad(gi_ctx* ctx, int dtype, const void* X, const float* img, float* dW, int n, int Hs, int Ws, int c, int ldx, int coffx,
+                int relu_in, float scale, float img_scale, const void* x2, int ld2, const float* scale2, const float* shift2, float* scratch,
+                int64_t scratch_floats) {
+  GI_REQUIRE(ctx && X && img && dW, "c1_wgrad: null pointer");
+  GI_REQUIRE(!x2 || (scale2 && shift2), "c1_wgrad: x2 without scale2 / shift2");
+  C1Affine aff;
+  aff.x2 = x2; aff.ld2 = ld2; aff.scale = scale2; aff.shift = shift2;
+  return op_c1_wgrad(ctx->stream, dtype, X, img, dW, n, Hs, Ws, c, ldx, coffx, relu_in, scale, img_scale, x2 ? &aff : nullptr, scratch,
+                     scratch_floats);
+}
+
+int gi_c1_wgrad_reduce(gi_ctx* ctx, const float* part, float* dW, int count, int blocks, float* scratch, int64_t scratch_floats) {
+  GI_REQUIRE(ctx && part && dW, "c1_wgrad_reduce: null pointer");
+  return op_c1_wgrad_reduce(ctx->stream, part, dW, count, blocks, scratch, scratch_floats);
+}
+
+int64_t gi_c1_head4_col_bytes(int n, int Hs, int Ws) { return op_c1_head4_col_bytes(n, Hs, Ws); }
+
+int gi_c1_head4_forward(gi_ctx* ctx, const void* X, const float* w, const float* bias, float* out, float* out2, int n, int Hs, int Ws, int ldx,
+                        int coffx, int relu_in, void* col_scratch) {
+  GI_REQUIRE(ctx && X && w && out && col_scratch, "c1_head4_forward: null pointer");
+  GI_REQUIRE(op_c1_head4_ok(GI_F16, 128, 4, Ws, ldx, coffx), "c1_head4_forward: Ws=%d ldx=%d coffx=%d unsupported", Ws, ldx, coffx);
+  return op_c1_head4_forward(ctx->stream, X, w, bias, out, out2, n, Hs, Ws, ldx, coffx, relu_in, col_scratch);
+}
+
+int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, int n, int Hs, int Ws, int ldout, int coffout) {
+  GI_REQUIRE(ctx && g && w && out, "c1_head4_dgrad: null pointer");
+  return op_c1_head4_dgrad(ctx->stream, g, w, out, n, Hs, Ws, ldout, coffout);
+}
+
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase) {
   GI_REQUIRE(ctx && w, "pack_weights: null pointer");
   return op_pack_weights(ctx->stream, dtype, w, ca, cb, w_packed, w_phase);

@@ -1569,6 +1569,7 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
     }
 #undef GI_C1G
     GI_LAUNCH_CHECK();
+    gi_note_kernel(c == 64 ? "c1_gather_mfma<4>" : "c1_gather_mfma<8>");
     return GI_OK;
   }
   if (gi_is_pow2(groups) && groups <= 32 && Ws % (256 / groups) == 0) {
@@ -1583,8 +1584,11 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
       hipLaunchKernelGGL(c1_gather_strip_kernel<float>, dim3(grid), dim3(256), lds, st, img, w, (char*)out, n, Hs, Ws, c, ldout,
                          coffout, act_out, in_scale, bias);
     GI_LAUNCH_CHECK();
+    gi_note_kernel("c1_gather_strip");
     return GI_OK;
   }
+  // the generic form splits a thread index into (pixel, 8-channel group) with a mask and a shift
+  GI_REQUIRE(gi_is_pow2(groups), "c1_gather: c=%d unsupported here (c / 8 must be a power of two)", c);
   const int grid = grid_for(total, 256, 256 * 16);
   if (dtype == GI_F16)
     hipLaunchKernelGGL(c1_gather_kernel<half_t>, dim3(grid), dim3(256), c * 16 * 4, st, img, w, (char*)out, n, Hs, Ws, c,
@@ -1593,6 +1597,7 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
     hipLaunchKernelGGL(c1_gather_kernel<float>, dim3(grid), dim3(256), c * 16 * 4, st, img, w, (char*)out, n, Hs, Ws, c,
                        ldout, coffout, act_out, in_scale, bias);
   GI_LAUNCH_CHECK();
+  gi_note_kernel("c1_gather");
   return GI_OK;
 }
 
@@ -1657,6 +1662,7 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
         hipLaunchKernelGGL(c1_scatter_fused_kernel<2>, dim3(gridf), dim3(256), lds_f, st, (const char*)X, w, bias, img, img2, Hs, Ws, TH, ldx, coffx, relu_in,
                            x2, ld2, sc2, sh2, fa, use_fa, post, out_scale);
       GI_LAUNCH_CHECK();
+      gi_note_kernel(c == 128 ? "c1_scatter_fused<4>" : "c1_scatter_fused<2>");
       return GI_OK;
     }
     if (c == 128)
@@ -1667,6 +1673,7 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
     hipLaunchKernelGGL(c1_col2im_kernel, dim3(grid_for(P, 256, 256 * 8)), dim3(256), 0, st, (const half_t*)col_scratch, bias, img, img2, n, Hs,
                        Ws, post, out_scale);
     GI_LAUNCH_CHECK();
+    gi_note_kernel(c == 128 ? "c1_col+col2im<4>" : "c1_col+col2im<2>");
     return GI_OK;
   }
   const int epc = dtype == GI_F16 ? 8 : 4;
@@ -1682,6 +1689,7 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
                        ldx, coffx, relu_in, post, out_scale);
   GI_LAUNCH_CHECK();
   if (img2) GI_HIP(hipMemcpyAsync(img2, img, (size_t)n * 4 * Hs * Ws * 4, hipMemcpyDeviceToDevice, st));
+  gi_note_kernel("c1_scatter");
   return GI_OK;
 }
 
@@ -1857,6 +1865,7 @@ int op_c1_head4_forward(hipStream_t st, const void* X, const float* w, const flo
   hipLaunchKernelGGL(c1_col2im_mc_kernel<4>, dim3(grid_for(P * 4, 256, 256 * 8)), dim3(256), 0, st, (const half_t*)col_scratch, bias, out, out2, n, Hs,
                      Ws, 1);
   GI_LAUNCH_CHECK();
+  gi_note_kernel("c1_head4");
   return GI_OK;
 }
 int op_c1_head4_dgrad(hipStream_t st, const float* g, const float* w, void* out, int n, int Hs, int Ws, int ldout, int coffout) {
@@ -1864,5 +1873,6 @@ int op_c1_head4_dgrad(hipStream_t st, const float* g, const float* w, void* out,
   const int64_t ngroups = (int64_t)n * Hs * Ws / 16;
   hipLaunchKernelGGL(c1_gather_mc4_kernel<8>, dim3(grid_for(ngroups, 4, 256 * 8)), dim3(256), 0, st, g, w, (char*)out, n, Hs, Ws, ldout, coffout);
   GI_LAUNCH_CHECK();
+  gi_note_kernel("c1_head4_dgrad");
   return GI_OK;
 }

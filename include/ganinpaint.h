@@ -512,6 +512,40 @@ int gi_wgrad_s2(gi_ctx* ctx, int dtype, const void* S, const void* L, float* dW,
 int64_t gi_wgrad_s2_scratch_bytes(int dtype, int n, int Hs, int Ws, int ca, int cb);
 int gi_wgrad_s2_ws(gi_ctx* ctx, int dtype, const void* S, const void* L, float* dW, int n, int Hs, int Ws,
                    int ca, int ldS, int cb, int ldL, int relu_S, float scale, float* scratch, int64_t scratch_bytes);
+/* ---- the single-channel layers on their own (test seam) ------------------------------------------------------------------
+ * The layers whose large side has ONE channel: img is fp32 (n,1,2Hs,2Ws), the feature side NHWC of type T with row pitch ld and
+ * channel offset coff, w the fp32 master [c][16] (tap = ky*4 + kx). Each call runs the dispatcher of csrc/c1.hip on the
+ * context's stream; gi_debug_last_kernel() names the form that served it ("c1_gather_mfma<4|8>", "c1_gather_strip", "c1_gather",
+ * "c1_scatter_fused<2|4>", "c1_col+col2im<2|4>", "c1_scatter", "c1_wgrad_mfma[,atomics]", "c1_wgrad[,atomics]", "c1_head4",
+ * "c1_head4_dgrad").
+ * gather: out[p][coffout + ch] = act(bias[ch] + sum_tap img[n,2y-1+ky,2x-1+kx] * in_scale * w[ch][tap]). bits (or NULL): one sign word
+ * per pixel (bit ch = [out > 0]) where the serving form writes them (fp16, c = 64); *bits_written says whether it did. */
+int gi_c1_gather(gi_ctx* ctx, int dtype, const float* img, const float* w, void* out, int n, int Hs, int Ws, int c,
+                 int ldout, int coffout, int act_out, float in_scale, const float* bias, unsigned long long* bits,
+                 int* bits_written);
+/* scatter: img = post(bias[0] + conv_transpose(relu?(X), w)) * out_scale, post 1 = tanh; img2 (or NULL) a second copy. col_scratch
+ * (or NULL): n*Hs*Ws*16 values of type fp16 for the fp16 matrix-core forms. x2 != NULL (fp16, c in {64, 128}, Ws % 32 == 0): channels
+ * [c/2, c) are not read from X but are relu(fma(x2[p][ch - c/2], scale2, shift2)) rounded to fp16, x2 of row pitch ld2. */
+int gi_c1_scatter(gi_ctx* ctx, int dtype, const void* X, const float* w, const float* bias, float* img, int n, int Hs,
+                  int Ws, int c, int ldx, int coffx, int relu_in, int post, float out_scale, void* col_scratch,
+                  float* img2, const void* x2, int ld2, const float* scale2, const float* shift2);
+/* dW[ch][tap] += scale * sum_p relu?(X[p][ch]) * img[n,2y-1+ky,2x-1+kx] * img_scale; x2 .. shift2 as above. scratch (or NULL,
+ * scratch_floats floats): the workgroups' partial sums, added in a fixed order; without it float atomics */
+int gi_c1_wgrad(gi_ctx* ctx, int dtype, const void* X, const float* img, float* dW, int n, int Hs, int Ws, int c, int ldx,
+                int coffx, int relu_in, float scale, float img_scale, const void* x2, int ld2, const float* scale2,
+                const float* shift2, float* scratch, int64_t scratch_floats);
+/* dW[i] += sum over `blocks` rows of part[block][count] in a fixed order; scratch (>= 64 * count floats, or NULL): a first
+ * stage over row ranges when there are 256 rows or more */
+int gi_c1_wgrad_reduce(gi_ctx* ctx, const float* part, float* dW, int count, int blocks, float* scratch,
+                       int64_t scratch_floats);
+/* the 4-class head (fp16, 128 input channels, w fp32 [c][16][4]): out = tanh(bias + conv_transpose(relu?(X), w)) as (n,4,2Hs,2Ws)
+ * fp32 (out2: a second copy or NULL), col_scratch of gi_c1_head4_col_bytes bytes; dgrad: out[p][coffout + ch] from the
+ * (n,4,2Hs,2Ws) fp32 gradient g */
+int64_t gi_c1_head4_col_bytes(int n, int Hs, int Ws);
+int gi_c1_head4_forward(gi_ctx* ctx, const void* X, const float* w, const float* bias, float* out, float* out2, int n,
+                        int Hs, int Ws, int ldx, int coffx, int relu_in, void* col_scratch);
+int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, int n, int Hs, int Ws, int ldout,
+                      int coffout);
 /* fp32 master [a][16][b] -> T [a][16*b] (w_packed) and T [4][b][4*a] (w_phase); either may be NULL */
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase);
 int gi_convert(gi_ctx* ctx, int dtype, const float* src, void* dst, int64_t count);      /* fp32 -> T */
