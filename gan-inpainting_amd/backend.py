@@ -144,6 +144,7 @@ PROTOTYPES = {
     "gi_wgrad_s2": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f]),
     "gi_conv_s2_forward_ex": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "gi_convT_s2_forward_ex": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "gi_debug_igemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp, _i, _vp]),
     "gi_stat_acc_words": (_i64, [_i]),
     "gi_stat_acc_read": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "gi_pack_weights": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "stat_acc.h"
+#include "igemm_plan.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -188,6 +189,35 @@ int gi_convT_s2_forward_ex(gi_ctx* ctx, int dtype, const void* in, const void* w
   const int rc = op_igemm(ctx->stream, dtype, 1, a);
   return_ex(a, ex);
   return rc;
+}
+
+int gi_debug_igemm_plan(int dtype, int mode, int n, int Hs, int Ws, int cin, int ldin, int cout, int ldout, int relu_in, int act_out,
+                        int64_t ws_bytes, int has_tickets, const gi_igemm_ex* ex, int offered, gi_igemm_plan_info* out) {
+  GI_REQUIRE(out, "debug_igemm_plan: null pointer");
+  static char dummy[8];   // stands for every operand: the plan only asks whether a pointer is null
+  IgemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = a.w = a.out = dummy;
+  if (ws_bytes > 0) { a.ws = (float*)dummy; a.ws_bytes = ws_bytes; }
+  a.tickets = has_tickets ? (unsigned*)dummy : nullptr;
+  a.n = n; a.Hs = Hs; a.Ws = Ws;
+  a.cin = cin; a.ldin = ldin; a.cout = cout; a.ldout = ldout;
+  a.relu_in = relu_in; a.act_out = act_out;
+  GI_TRY(apply_ex(a, ex));
+  IgemmFold fold = {};
+  if ((offered & 1) && a.stat_acc) { fold.bn.groups = 1; fold.bn.acc = a.stat_acc; fold.lddst = ldout; fold.act = GI_ACT_RELU; a.fold = &fold; }
+  if ((offered & 2) && a.mask_bits) { a.c1w_img = (const float*)dummy; a.c1w_part = (float*)dummy; a.c1w_part_floats = (int64_t)1 << 40; a.c1w_scale = 1.f; }
+  if (offered & 4) a.pool2 = 1;
+  if (offered & 8) a.bias = (const float*)dummy;
+  IgemmPlan p;
+  GI_TRY(gi_igemm_plan(dtype, mode, a, &p));
+  gi_igemm_returns(p, a);
+  memset(out, 0, sizeof(*out));
+  strncpy(out->name, p.name, sizeof(out->name) - 1);
+  out->grid = p.grid; out->splitk = p.splitk > 1 ? p.splitk : 1; out->ntiles_out = a.ntiles_out;
+  out->mask_applied = a.mask_applied; out->bwd_applied = a.bwd_applied; out->stat_used = a.stat_used;
+  out->c1w_applied = a.c1w_applied; out->c1w_blocks = a.c1w_blocks; out->pool_applied = a.pool_applied; out->fold_applied = a.fold_applied;
+  return GI_OK;
 }
 
 int64_t gi_stat_acc_words(int c) { return gi_stat_block_words(c, GI_STAT_MAXREP); }

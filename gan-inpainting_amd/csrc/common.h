@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <mutex>
 #include <type_traits>
 
 #include "../../include/ganinpaint.h"
@@ -124,12 +125,27 @@ __device__ __forceinline__ f4_t gi_ordered_sum_f4(const f4_t* part, int64_t stri
 // (not the data-parallel layout, which is one process per GPU) must repeat it per device
 struct GiDevOnce {
   unsigned long long mask = 0;
-  bool first() {
+  std::mutex mu;
+  bool first() {   // (claims the device before the caller has done the work: a second host thread can get past it early; use once())
     int d = 0;
     (void)hipGetDevice(&d);
     const unsigned long long b = 1ull << (d & 63);
     const unsigned long long old = __atomic_fetch_or(&mask, b, __ATOMIC_RELAXED);
     return (old & b) == 0;
+  }
+  // f() once per device: the device's bit is published only after f() has succeeded, and a second host thread waits for it (the
+  // mutex is taken on the first calls per device only, never on the steady-state path)
+  template <typename F>
+  hipError_t once(F&& f) {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    const unsigned long long b = 1ull << (d & 63);
+    if (__atomic_load_n(&mask, __ATOMIC_ACQUIRE) & b) return hipSuccess;
+    std::lock_guard<std::mutex> lock(mu);
+    if (__atomic_load_n(&mask, __ATOMIC_RELAXED) & b) return hipSuccess;
+    const hipError_t e = f();
+    if (e == hipSuccess) __atomic_fetch_or(&mask, b, __ATOMIC_RELEASE);
+    return e;
   }
 };
 
@@ -164,6 +180,17 @@ struct GiDevOnce {
     int _s = (expr);                \
     if (_s != GI_OK) return _s;     \
   } while (0)
+
+// Launch of a kernel with dynamic LDS: raises the kernel's limit to lds_attr bytes once per device (its own flag per instantiation),
+// then launches `lds` bytes. Kernel: a __global__ function taking one argument struct P by value.
+template <auto Kernel, typename P>
+int gi_launch_lds(dim3 grid, int block, int lds, int lds_attr, hipStream_t st, const P& p) {
+  static GiDevOnce attr_set;
+  GI_HIP(attr_set.once([&] { return hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); }));
+  hipLaunchKernelGGL(Kernel, grid, dim3(block), lds, st, p);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
 
 struct gi_ctx {
   int device;
@@ -252,7 +279,8 @@ struct IgemmArgs {
   const IgemmFold* fold; int fold_applied;
 };
 constexpr int GI_IGEMM_TICKETS = 1024;
-int op_igemm(hipStream_t st, int dtype, int phase_mode, IgemmArgs& a);
+// mode 0: the stride-2 gather, 1: sub-pixel phases, 2: Conv2d 3x3 / s1 / p1 (fp16). igemm_plan.hip picks the kernel.
+int op_igemm(hipStream_t st, int dtype, int mode, IgemmArgs& a);
 
 struct WgradArgs {
   const void* S;   // small tensor (n,Hs,Ws,ca), ld=ldS, channel offset coffS

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "stat_acc.h"
+#include "igemm_plan.h"
 
 namespace {
 
@@ -509,131 +510,46 @@ int launch_cfg(hipStream_t st, const KP& kp, dim3 grid) {
   constexpr int STAGE_BYTES = F16 ? (BM + BN) * 128 : 32 * (BM + 1 + BN + 1) * 4;
   constexpr int EPI = BM * (BN + 16 / (int)sizeof(T)) * (int)sizeof(T) + WGM * BN * 2 * 4;
   constexpr int LDS = (2 * STAGE_BYTES > EPI ? 2 * STAGE_BYTES : EPI);
-  auto kern = igemm_kernel<T, PHASE, BM, BN, WGM, WGN>;
-  static GiDevOnce attr_set;
-  if (attr_set.first()) {
-    GI_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, kp);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
+  return gi_launch_lds<igemm_kernel<T, PHASE, BM, BN, WGM, WGN>>(grid, 256, LDS, LDS, st, kp);
 }
 
 template <typename T, int PHASE>
-int run(hipStream_t st, IgemmArgs& a) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  constexpr int BK = 8 * EPC;
-  GI_REQUIRE(a.cin % BK == 0, "igemm: cin=%d must be a multiple of %d", a.cin, BK);
-  GI_REQUIRE(a.cout % 64 == 0, "igemm: cout=%d must be a multiple of 64", a.cout);
-  GI_REQUIRE(a.ldin % EPC == 0 && a.coffin % EPC == 0 && a.ldout % EPC == 0 && a.coffout % EPC == 0,
-             "igemm: leading dims / channel offsets must be 16-byte aligned");
+int run(hipStream_t st, const IgemmPlan& p, const IgemmArgs& a) {
+  constexpr int BK = 8 * 16 / (int)sizeof(T);
+  const bool finish = p.finish_launch;   // the splits go to the workspace, a second launch adds them up and runs the epilogue
   KP kp;
   kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out;
-  kp.bias = a.bias; kp.partials = a.stat_acc ? nullptr : a.partials; kp.ws = a.ws; kp.tickets = nullptr;
-  kp.stat_acc = a.stat_acc; kp.stat_pg = a.stat_pg; kp.stat_reps = a.stat_reps > 0 ? a.stat_reps : 1;
-  a.stat_used = a.stat_acc ? 1 : 0;
+  kp.bias = a.bias; kp.partials = (a.stat_acc || finish) ? nullptr : a.partials; kp.ws = a.ws; kp.tickets = p.fixup ? a.tickets : nullptr;
+  kp.stat_acc = finish ? nullptr : a.stat_acc; kp.stat_pg = a.stat_pg; kp.stat_reps = a.stat_reps > 0 ? a.stat_reps : 1;
   kp.M = a.n * a.Hs * a.Ws; kp.Hs = a.Hs; kp.Ws = a.Ws;
   kp.cin = a.cin; kp.ldin = a.ldin; kp.coffin = a.coffin;
   kp.cout = a.cout; kp.ldout = a.ldout; kp.coffout = a.coffout;
   kp.Ktot = (PHASE ? 4 : 16) * a.cin;
   kp.nk = kp.Ktot / BK;
+  kp.splitk = p.splitk; kp.kt_per_split = p.kt_per_split;
   kp.relu_in = a.relu_in; kp.act_out = a.act_out;
   if (PHASE) { kp.Hin = a.Hs; kp.Win = a.Ws; kp.Hout = 2 * a.Hs; kp.Wout = 2 * a.Ws; }
   else { kp.Hin = 2 * a.Hs; kp.Win = 2 * a.Ws; kp.Hout = a.Hs; kp.Wout = a.Ws; }
-  const int64_t in_elems = (int64_t)a.n * kp.Hin * kp.Win * a.ldin;
-  kp.in_elems = in_elems;
+  kp.in_elems = (int64_t)a.n * kp.Hin * kp.Win * a.ldin;
   const int64_t out_pixels = (int64_t)a.n * kp.Hout * kp.Wout;
-  GI_REQUIRE(in_elems < (1ll << 31) && out_pixels * a.ldout < (1ll << 31), "igemm: tensor too large for 32-bit offsets");
-
-  const bool wide = (a.cout % 128 == 0);
-  int BM = wide ? 128 : 256, BN = wide ? 128 : 64;
-  const int phases = PHASE ? 4 : 1;
-  int mt = (kp.M + BM - 1) / BM, nt = a.cout / BN;
-  int tiles = mt * nt * phases;
-  int splitk = 1;
-  // in-kernel fix-up: the last arriver reads splits x tile bytes on ONE CU (~100 GB/s), so the split count is capped
-  // and very small M gets 128 x 64 tiles instead (twice the workgroups for the same tail)
-  const int fix = gi_opt(GI_OPT_IGEMM_FIXUP);   // GI_IGEMM_FIXUP=0: finish-kernel path
-  int fix_max = gi_tune("GI_IGEMM_FIX_MAXSPLIT", 8);
-  if (fix_max < 2) fix_max = 8;
-  bool fixup = fix && a.tickets && a.ws && a.force_splitk == 0 && tiles < 256 && kp.nk >= 8;
-  bool half_n = false;
-  if (fixup) {
-    if (wide && tiles * fix_max < 256) { half_n = true; BN = 64; nt = a.cout / BN; tiles = mt * nt * phases; }
-    splitk = (256 + tiles - 1) / tiles;
-    if (splitk > fix_max) splitk = fix_max;
-    if (splitk > kp.nk / 4) splitk = kp.nk / 4;
-    if (splitk < 1) splitk = 1;
-    if (tiles > GI_IGEMM_TICKETS || a.ws_bytes < (int64_t)splitk * tiles * BM * BN * 4) {
-      fixup = false; splitk = 1;
-      if (half_n) { half_n = false; BN = 128; nt = a.cout / BN; tiles = mt * nt * phases; }
-    }
-  }
-  if (fixup) {
-  } else if (a.force_splitk > 0) splitk = a.force_splitk;
-  else if (tiles < 256 && kp.nk >= 8) {   // fewer workgroups than CUs: split the reduction
-    const int target = gi_tune("GI_IGEMM_SPLIT_BLOCKS", 384);   // workgroups to aim for
-    splitk = (target + tiles - 1) / tiles;
-    if (splitk > kp.nk / 4) splitk = kp.nk / 4;
-    if (splitk > 64) splitk = 64;
-    if (splitk < 1) splitk = 1;
-  }
-  if (splitk > 1 && (a.ws == nullptr || a.ws_bytes < out_pixels * a.cout * 4)) splitk = 1;
-  kp.kt_per_split = (kp.nk + splitk - 1) / splitk;
-  splitk = (kp.nk + kp.kt_per_split - 1) / kp.kt_per_split;
-  kp.splitk = splitk;
-  kp.ws_stride = 0;
-  if (splitk <= 1) fixup = false;
-  if (fixup) kp.tickets = a.tickets;
-  if (splitk > 1 && !fixup) {
-    // scratch for one buffer per split: plain stores + a summing finish pass (deterministic, no memset);
-    // otherwise fp32 atomics into a single zeroed buffer
-    if (a.ws_bytes >= (int64_t)splitk * out_pixels * a.cout * 4) kp.ws_stride = out_pixels * a.cout;
-    else GI_HIP(hipMemsetAsync(a.ws, 0, out_pixels * a.cout * 4, st));
-    kp.partials = nullptr;
-    kp.stat_acc = nullptr;
-  }
-  GI_REQUIRE(!a.stat_acc || a.stat_pg == 0 || a.stat_pg % 256 == 0, "igemm: stat_pg=%d must be a multiple of 256", a.stat_pg);
-  dim3 grid(mt, nt, phases * splitk);
-  if (half_n) GI_TRY((launch_cfg<T, PHASE, 128, 64, 2, 2>(st, kp, grid)));
-  else if (wide) GI_TRY((launch_cfg<T, PHASE, 128, 128, 2, 2>(st, kp, grid)));
+  kp.ws_stride = (finish && !p.atomics_ws) ? out_pixels * a.cout : 0;
+  if (p.atomics_ws) GI_HIP(hipMemsetAsync(a.ws, 0, out_pixels * a.cout * 4, st));
+  const dim3 grid(p.mtiles, p.ntiles, (PHASE ? 4 : 1) * p.splitk);
+  if (p.half_n) GI_TRY((launch_cfg<T, PHASE, 128, 64, 2, 2>(st, kp, grid)));
+  else if (p.BM == 128) GI_TRY((launch_cfg<T, PHASE, 128, 128, 2, 2>(st, kp, grid)));
   else GI_TRY((launch_cfg<T, PHASE, 256, 64, 4, 1>(st, kp, grid)));
-  gi_note_kernel(std::is_same<T, float>::value ? (fixup ? "igemm<f32,fixup>" : (splitk > 1 ? "igemm<f32,splitk>" : "igemm<f32>"))
-                                               : (fixup ? "igemm<f16,fixup>" : (splitk > 1 ? "igemm<f16,splitk>" : "igemm<f16>")));
-  a.ntiles_out = mt * phases;
-  if (splitk > 1 && !fixup) {
-    const int RL = 256 / (a.cout / 4) > 0 ? 256 / (a.cout / 4) : 1;   // row lanes per block
-    int rpb = 64;
-    while (rpb > RL && (out_pixels + rpb - 1) / rpb < 256) rpb >>= 1;   // fill the chip on small tensors
-    if (rpb < RL) rpb = RL;
-    const int blocks = (int)((out_pixels + rpb - 1) / rpb);
-    GI_REQUIRE(a.cout <= 1024, "igemm split-K finish: cout=%d > 1024", a.cout);
-    hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(blocks), dim3(256), 0, st, a.ws, a.bias, (char*)a.out,
-                       a.partials, out_pixels, a.cout, a.ldout, a.coffout, a.act_out, rpb, kp.ws_stride > 0 ? splitk : 1,
+  if (finish) {
+    hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(p.finish_blocks), dim3(256), 0, st, a.ws, a.bias, (char*)a.out,
+                       a.partials, out_pixels, a.cout, a.ldout, a.coffout, a.act_out, p.finish_rows, kp.ws_stride > 0 ? p.splitk : 1,
                        kp.ws_stride, a.partials ? nullptr : a.stat_acc, (int64_t)a.stat_pg * (PHASE ? 4 : 1), kp.stat_reps);
-    a.stat_used = (a.stat_acc && !a.partials) ? 1 : 0;
     GI_LAUNCH_CHECK();
-    a.ntiles_out = blocks;
   }
   return GI_OK;
 }
 
 }  // namespace
 
-int op_igemm3(hipStream_t st, int mode, IgemmArgs& a);   // igemm3.hip: 256xBN tiles, LDS-DMA ring
-int op_igemm7(hipStream_t st, int mode, IgemmArgs& a);   // igemm7.hip: 128xBN tiles, 4-stage ring, split-K with in-kernel fix-up
-
-int op_igemm(hipStream_t st, int dtype, int phase_mode, IgemmArgs& a) {
-  // GI_IGEMM_VARIANT: 3 = LDS-DMA kernels (default), 1 = the register-staged kernel of this file only (what fp32 always runs)
-  const int variant = gi_opt(GI_OPT_IGEMM_VARIANT);
-  if (dtype == GI_F16 && a.force_splitk == 0 && variant >= 3) {
-    int rc = op_igemm3(st, phase_mode, a);
-    if (rc != GI_ERR_UNSUPPORTED) return rc;
-    rc = op_igemm7(st, phase_mode, a);      // small-M layers: deep LDS-DMA ring + in-kernel split-K reduction
-    if (rc != GI_ERR_UNSUPPORTED) return rc;
-  }
-  if (dtype == GI_F16) return phase_mode ? run<half_t, 1>(st, a) : run<half_t, 0>(st, a);
-  if (dtype == GI_F32) return phase_mode ? run<float, 1>(st, a) : run<float, 0>(st, a);
-  gi_set_error("igemm: bad dtype %d", dtype);
-  return GI_ERR_INVALID;
+int launch_igemm(hipStream_t st, int dtype, const IgemmPlan& p, const IgemmArgs& a) {
+  if (dtype == GI_F16) return p.mode ? run<half_t, 1>(st, p, a) : run<half_t, 0>(st, p, a);
+  return p.mode ? run<float, 1>(st, p, a) : run<float, 0>(st, p, a);
 }

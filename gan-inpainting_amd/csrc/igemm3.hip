@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "stat_acc.h"
+#include "igemm_plan.h"
 
 namespace {
 
@@ -363,7 +364,7 @@ char* g_zero_page[16] = {nullptr};
 
 }  // namespace
 
-// the zero page padding taps read (shared with igemm5.hip); allocated on first use, one per device
+// the zero page padding taps read (shared with igemm5 / 7 / 8 and wgrad2.hip); allocated on first use, one per device
 const char* gi_igemm3_zero_page(int dev) {
   if (!g_zero_page[dev & 15]) {
     if (hipMalloc((void**)&g_zero_page[dev & 15], 8192) != hipSuccess) return nullptr;
@@ -372,41 +373,14 @@ const char* gi_igemm3_zero_page(int dev) {
   return g_zero_page[dev & 15];
 }
 
-int op_igemm5(hipStream_t st, int mode, IgemmArgs& a);   // igemm5.hip: halo-resident kernels (modes 0 and 1)
-
-// mode: 0 = Conv2d 4x4/s2/p1 gather, 1 = sub-pixel phases (ConvTranspose2d forward / Conv2d dgrad),
-//       2 = Conv2d 3x3/s1/p1 (VGG features; weights [cout][9*cin], tap-major).
-// returns GI_ERR_UNSUPPORTED when the shape is not served by this kernel (caller falls back)
-int op_igemm3(hipStream_t st, int mode, IgemmArgs& a) {
-  if (a.cin % 64 != 0 || a.cout % 64 != 0 || a.cin > 2048) return GI_ERR_UNSUPPORTED;
-  const int use5 = gi_opt(GI_OPT_IGEMM5);   // GI_IGEMM5: bit 0 / 1 / 2 = halo-resident kernel for mode 1 / 0 / 2 (default all)
-  if ((mode == 1 && (use5 & 1)) || (mode == 0 && (use5 & 2)) || (mode == 2 && (use5 & 4))) {
-    const int rc = op_igemm5(st, mode, a);
-    if (rc != GI_ERR_UNSUPPORTED) return rc;
-  }
-  const int M = a.n * a.Hs * a.Ws;
-  const int nph = mode == 1 ? 4 : 1;
-  int BN = (a.cout % 128 == 0) ? 128 : 64;
-  if (mode != 2) {   // too few tiles to fill 256 CUs: the split-K path of igemm.hip serves those layers
-    const int tiles = ((M + 255) / 256) * (a.cout / BN) * nph;
-    if (tiles < 128) return GI_ERR_UNSUPPORTED;
-    // 128..255 tiles leave CUs idle (one 8-wave workgroup per CU): 64-wide N tiles double the workgroups
-    const int narrow = gi_tune("GI_IGEMM3_NARROW", 1);
-    if (narrow && BN == 128 && tiles < 256) BN = 64;
-  }
-  int dev = 0;
-  GI_HIP(hipGetDevice(&dev));
-  if (!g_zero_page[dev & 15]) {
-    GI_HIP(hipMalloc((void**)&g_zero_page[dev & 15], 8192));
-    GI_HIP(hipMemset(g_zero_page[dev & 15], 0, 8192));
-  }
+int launch_igemm3(hipStream_t st, const IgemmPlan& p, const IgemmArgs& a) {
+  const int mode = p.mode;
   KP3 kp;
-  kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out; kp.zero = g_zero_page[dev & 15];
+  kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out; kp.zero = gi_igemm_zero_page();
+  if (!kp.zero) { gi_set_error("igemm3: no zero page"); return GI_ERR_HIP; }
   kp.bias = a.bias; kp.partials = a.stat_acc ? nullptr : a.partials;
   kp.stat_acc = a.stat_acc; kp.stat_pg = a.stat_pg; kp.stat_reps = a.stat_reps > 0 ? a.stat_reps : 1;
-  a.stat_used = a.stat_acc ? 1 : 0;
-  GI_REQUIRE(!a.stat_acc || a.stat_pg == 0 || a.stat_pg % 256 == 0, "igemm3: stat_pg=%d must be a multiple of 256", a.stat_pg);
-  kp.M = M; kp.Hs = a.Hs; kp.Ws = a.Ws;
+  kp.M = a.n * a.Hs * a.Ws; kp.Hs = a.Hs; kp.Ws = a.Ws;
   kp.cin = a.cin; kp.ldin = a.ldin; kp.coffin = a.coffin;
   kp.cout = a.cout; kp.ldout = a.ldout; kp.coffout = a.coffout;
   kp.Ktot = (mode == 1 ? 4 : (mode == 2 ? 9 : 16)) * a.cin;
@@ -414,63 +388,22 @@ int op_igemm3(hipStream_t st, int mode, IgemmArgs& a) {
   kp.relu_in = a.relu_in; kp.act_out = a.act_out;
   kp.relu_cend = a.relu_cend > 0 ? a.relu_cend : a.cin;
   kp.dbg = 0;
-#ifdef GI_ABLATION   // timing-only ablation kernels compute wrong results: compiled only with `build.sh -DGI_ABLATION`
-  { const char* e = getenv("GI_IGEMM3_DBG"); kp.dbg = e ? atoi(e) : 0; }
-#endif
   if (mode == 1) { kp.Hin = a.Hs; kp.Win = a.Ws; kp.Hout = 2 * a.Hs; kp.Wout = 2 * a.Ws; }
   else if (mode == 2) { kp.Hin = a.Hs; kp.Win = a.Ws; kp.Hout = a.Hs; kp.Wout = a.Ws; }
   else { kp.Hin = 2 * a.Hs; kp.Win = 2 * a.Ws; kp.Hout = a.Hs; kp.Wout = a.Ws; }
-  GI_REQUIRE((int64_t)a.n * kp.Hin * kp.Win * a.ldin < (1ll << 31) && (int64_t)a.n * kp.Hout * kp.Wout * a.ldout < (1ll << 31),
-             "igemm3: tensor too large for 32-bit offsets");
-  kp.mtiles = (M + 255) / 256;
-  kp.ntiles = a.cout / BN;
-  const int nyz = kp.ntiles * nph;
-  const int grid = ((kp.mtiles + 7) / 8) * 8 * nyz;
-  constexpr int LDS_MAX = 3 * (256 + 128) * 128;
-  const int ring = 3 * (256 + BN) * 128, epi = 256 * (BN + 8) * 2 + 4 * BN * 8;
-  const int LDS = ring > epi ? ring : epi;
-  static GiDevOnce attr_set[6];
-  const void* fn[6] = {(const void*)igemm3_kernel<0, 128, 8>, (const void*)igemm3_kernel<1, 128, 8>, (const void*)igemm3_kernel<2, 128, 8>,
-                       (const void*)igemm3_kernel<0, 64, 8>,  (const void*)igemm3_kernel<1, 64, 8>,  (const void*)igemm3_kernel<2, 64, 8>};
-  const int vi = (BN == 64 ? 3 : 0) + mode;
-  if (attr_set[vi].first()) { GI_HIP(hipFuncSetAttribute(fn[vi], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX)); }
-  const dim3 g(grid), b(512);
-#ifdef GI_ABLATION
-  if (kp.dbg && vi == 1) {   // timing-only ablation builds of the PHASE / 128 kernel (GI_IGEMM3_DBG, tools only)
-    static GiDevOnce dbg_attr;
-    if (dbg_attr.first()) {
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 15>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      GI_HIP(hipFuncSetAttribute((const void*)igemm3_kernel<1, 128, 8, 31>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    }
-    switch (kp.dbg) {
-      case 1: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 1>), g, b, LDS, st, kp); break;
-      case 2: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 2>), g, b, LDS, st, kp); break;
-      case 4: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 4>), g, b, LDS, st, kp); break;
-      case 7: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 7>), g, b, LDS, st, kp); break;
-      case 8: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 8>), g, b, LDS, st, kp); break;
-      case 15: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 15>), g, b, LDS, st, kp); break;
-      default: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8, 31>), g, b, LDS, st, kp); break;
-    }
-    GI_LAUNCH_CHECK();
-    a.ntiles_out = kp.mtiles * nph;
-    return GI_OK;
+  kp.mtiles = p.mtiles;
+  kp.ntiles = p.ntiles;
+#define GI_K3(V, MODE_, BN_, NAME) case V: return gi_launch_lds<igemm3_kernel<MODE_, BN_, 8>>(dim3(p.grid), 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
+#ifdef GI_ABLATION   // timing-only ablation kernels compute wrong results: compiled only with `build.sh -DGI_ABLATION`
+  { const char* e = getenv("GI_IGEMM3_DBG"); kp.dbg = e ? atoi(e) : 0; }
+#define GI_K3D(D_) case D_: return gi_launch_lds<igemm3_kernel<1, 128, 8, D_>>(dim3(p.grid), 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
+  if (kp.dbg && p.variant == 1) switch (kp.dbg) {   // timing-only ablation builds of the PHASE / 128 kernel (GI_IGEMM3_DBG, tools only)
+    GI_K3D(1) GI_K3D(2) GI_K3D(4) GI_K3D(7) GI_K3D(8) GI_K3D(15)
+    default: return gi_launch_lds<igemm3_kernel<1, 128, 8, 31>>(dim3(p.grid), 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
   }
+#undef GI_K3D
 #endif
-  switch (vi) {
-    case 0: hipLaunchKernelGGL((igemm3_kernel<0, 128, 8>), g, b, LDS, st, kp); break;
-    case 1: hipLaunchKernelGGL((igemm3_kernel<1, 128, 8>), g, b, LDS, st, kp); break;
-    case 2: hipLaunchKernelGGL((igemm3_kernel<2, 128, 8>), g, b, LDS, st, kp); break;
-    case 3: hipLaunchKernelGGL((igemm3_kernel<0, 64, 8>), g, b, LDS, st, kp); break;
-    case 4: hipLaunchKernelGGL((igemm3_kernel<1, 64, 8>), g, b, LDS, st, kp); break;
-    default: hipLaunchKernelGGL((igemm3_kernel<2, 64, 8>), g, b, LDS, st, kp); break;
-  }
-  { static const char* nm[6] = {"igemm3<0,128>", "igemm3<1,128>", "igemm3<2,128>", "igemm3<0,64>", "igemm3<1,64>", "igemm3<2,64>"}; gi_note_kernel(nm[vi]); }
-  GI_LAUNCH_CHECK();
-  a.ntiles_out = kp.mtiles * nph;
-  return GI_OK;
+  switch (p.variant) { GI_IGEMM3_KERNELS(GI_K3) }
+#undef GI_K3
+  return GI_ERR_INVALID;
 }

@@ -26,9 +26,6 @@
 #include "stat_acc.h"
 #include "halo_args.h"
 
-const char* gi_igemm3_zero_page(int dev);   // igemm3.hip
-int op_igemm8_launch(hipStream_t st, int mode, bool dual, bool relu, int grid, const KP5& kp, int bn);   // igemm8.hip
-
 namespace {
 
 __device__ __forceinline__ h8_t relu5(h8_t v) {
@@ -730,172 +727,30 @@ __global__ void __launch_bounds__(512, 2) igemm6_kernel(KP5 p) {
 
 }  // namespace
 
-// mode 1 (sub-pixel phases) and mode 0 (stride-2 gather). Returns GI_ERR_UNSUPPORTED for shapes it does not serve
-// (the caller falls back to igemm3).
-int op_igemm5(hipStream_t st, int mode, IgemmArgs& a) {
-  if (mode < 0 || mode > 2) return GI_ERR_UNSUPPORTED;
-  if (a.cin % 64 != 0 || a.cout % 64 != 0 || a.cin > 2048) return GI_ERR_UNSUPPORTED;
-  if (!gi_is_pow2(a.Ws) || a.Ws < 8) return GI_ERR_UNSUPPORTED;
-  const int TW = a.Ws < 32 ? a.Ws : 32, TH = 256 / TW;
-  if (a.Hs % TH != 0) return GI_ERR_UNSUPPORTED;
-  if (mode == 2 ? (TH + 2) * (TW + 2) > 384 : (TH + 1) * (TW + ((mode == 1 && a.cout % 128 != 0) ? 2 : 1)) > 320) return GI_ERR_UNSUPPORTED;
-  int BN = (a.cout % 128 == 0) ? 128 : 64;
-  const int nph = mode == 1 ? 4 : 1;
-  const int tiles_x = a.Ws / TW, tiles_per_img = tiles_x * (a.Hs / TH);
-  const int mtiles = a.n * tiles_per_img;
-  if (mode != 2 && mtiles * (a.cout / BN) * nph < 128) return GI_ERR_UNSUPPORTED;
-  if (mode == 0 && BN == 128 && mtiles * (a.cout / BN) < 256) {
-    // 128..255 workgroups on 256 CUs (generator d4 at 256x256, bs=32): 64-wide N tiles double them
-    const int narrow = gi_tune("GI_IGEMM5_NARROW", 1);
-    if (narrow) BN = 64;
-  }
-  const bool dual = mode == 1 && BN == 64;     // 64-channel N tiles: both px phases per workgroup (MODE 3)
-  int dev = 0;
-  GI_HIP(hipGetDevice(&dev));
-  const char* zero = gi_igemm3_zero_page(dev);
-  if (!zero) return GI_ERR_HIP;
-  const int64_t in_px = (int64_t)a.n * a.Hs * a.Ws * (mode == 0 ? 4 : 1), out_px = (int64_t)a.n * a.Hs * a.Ws * (mode == 1 ? 4 : 1);
-  GI_REQUIRE(in_px * a.ldin < (1ll << 31) && out_px * a.ldout < (1ll << 31), "igemm5: tensor too large for 32-bit offsets");
+// igemm5 (GI_FAM_IGEMM5) and igemm6 (GI_FAM_IGEMM6); the kernel tables are in igemm_plan.h
+int launch_igemm5(hipStream_t st, const IgemmPlan& p, const IgemmArgs& a) {
   KP5 kp;
-  kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out; kp.zero = zero;
-  kp.bias = a.bias; kp.partials = a.stat_acc ? nullptr : a.partials;
-  kp.stat_acc = a.stat_acc; kp.stat_pg = a.stat_pg; kp.stat_reps = a.stat_reps > 0 ? a.stat_reps : 1;
-  a.stat_used = a.stat_acc ? 1 : 0;
-  GI_REQUIRE(!a.stat_acc || a.stat_pg == 0 || a.stat_pg % (a.Hs * a.Ws) == 0, "igemm5: stat_pg=%d must be whole images", a.stat_pg);
-  kp.Hs = a.Hs; kp.Ws = a.Ws; kp.n = a.n; kp.TH = TH; kp.TW = TW;
-  kp.tiles_x = tiles_x; kp.tiles_per_img = tiles_per_img; kp.mtiles = mtiles;
-  kp.cin = a.cin; kp.ldin = a.ldin; kp.coffin = a.coffin;
-  kp.cout = a.cout; kp.ldout = a.ldout; kp.coffout = a.coffout;
-  kp.nchunk = a.cin / 64;
-  kp.relu_in = a.relu_in; kp.act_out = a.act_out;
-  kp.relu_cend = a.relu_cend > 0 ? a.relu_cend : a.cin;
-  kp.mask = (const char*)a.mask; kp.ldmask = a.ldmask; kp.coffmask = a.coffmask; kp.mask_slope = a.mask_slope;
-  kp.add = a.mask ? (const char*)a.add : nullptr; kp.ldadd = a.ldadd; kp.coffadd = a.coffadd;
-  kp.mask_bits = nullptr;
-  kp.c1w_img = nullptr; kp.c1w_part = nullptr; kp.c1w_scale = 0.f; kp.c1w_skip_out = 0;
-  a.c1w_applied = 0; a.c1w_blocks = 0;
-  kp.dbg_epi = 0;
-  kp.pool = 0;
-  a.pool_applied = 0;
-#ifdef GI_ABLATION
-  { const char* e = getenv("GI_EPI_DBG"); if (e) kp.dbg_epi = atoi(e); }
-#endif
-  kp.bwd_acc = nullptr; kp.bwd_c0 = 0; kp.bwd_c = a.cout;
-  if (a.mask) {
-    GI_REQUIRE(a.ldmask % 8 == 0 && a.coffmask % 8 == 0 && out_px * a.ldmask < (1ll << 31), "igemm5: mask layout");
-    GI_REQUIRE(!a.add || (a.ldadd % 8 == 0 && a.coffadd % 8 == 0 && out_px * a.ldadd < (1ll << 31)), "igemm5: add layout");
-    a.mask_applied = 1;
-  }
-  kp.ntiles = a.cout / BN;
-  const int nyz = kp.ntiles * (dual ? 2 : nph);
-  const int grid = ((mtiles + 7) / 8) * 8 * nyz;
-  const int BNk = dual ? 128 : BN;             // columns of the workgroup tile
-  const int ring = 2 * (mode == 2 ? 384 : 320) * 128 + 3 * BNk * 128, epi = 256 * (BNk + 8) * 2 + 4 * BNk * 8;
-  const int LDS = ring > epi ? ring : epi;
-  static GiDevOnce attr[6];
-  const void* fn[6] = {(const void*)igemm5_kernel<0, 128>, (const void*)igemm5_kernel<1, 128>, (const void*)igemm5_kernel<2, 128>,
-                       (const void*)igemm5_kernel<0, 64>,  (const void*)igemm5_kernel<1, 64>,  (const void*)igemm5_kernel<2, 64>};
-  // igemm8 (igemm8.hip): the same tile on four waves, two workgroups per CU. GI_IGEMM8: 0 off, 1 (default) layers whose grid
-  // gives every CU at least two workgroups (with one per CU half the wave slots stay empty: measured d3 / u4 / critic conv4,
-  // 256 workgroups, 10 - 16 % slower than igemm6; every layer with >= 512 workgroups 3 - 16 % faster), 2 every eligible layer
-  // GI_IGEMM6=0 (the first-generation halo kernels: no buffer-descriptor LDS-DMA anywhere) switches igemm8 off as well
-  const int use8 = gi_opt(GI_OPT_IGEMM6) ? gi_opt(GI_OPT_IGEMM8) : 0;
-  // (the 3x3 mode: 128-column tiles on 32-wide patches, no fused input ReLU; VGG-19 from conv2_1 to conv4_4)
-  const bool take8 = use8 && (mode != 2 || (TW == 32 && !a.relu_in)) && (dual || BN == 128 || mode == 2) && a.cin % (mode == 0 ? 64 : 32) == 0 && TW >= 16 && in_px * a.ldin * 2 < (1ll << 31) &&
-      (int64_t)a.cout * (mode == 1 ? 4 : (mode == 2 ? 9 : 16)) * a.cin * 2 * (dual ? 2 : 1) < (1ll << 31) && !(mode == 0 && a.relu_in) &&
-      (use8 >= 2 || grid >= gi_tune("GI_IGEMM8_MINGRID", 512));
-  // fused BatchNorm-backward reduction (the dual-px / 64-column tiles do not take it; nor a launch with a mask; a column range only igemm8)
-  const bool bwd_range = a.bwd_c > 0 && (a.bwd_c0 != 0 || a.bwd_c != a.cout);
-  if (a.bwd_acc && !a.mask && mode != 2 && a.cout % 128 == 0 && BN == 128 && (!bwd_range || (take8 && a.bwd_c0 % 128 == 0 && a.bwd_c % 128 == 0 && a.bwd_c0 + a.bwd_c <= a.cout))) {
-    const int64_t px_per_tile = 256 * (mode == 1 ? 4 : 1);          // output pixels per M tile over all phases
-    GI_REQUIRE(a.bwd_ldx % 8 == 0 && out_px * a.bwd_ldx < (1ll << 31) && (a.bwd_pg == 0 || a.bwd_pg % px_per_tile == 0) && a.coffout == 0,
-               "igemm5: fused BatchNorm-backward reduction: layout");
-    kp.bwd_x = (const char*)a.bwd_x; kp.bwd_ldx = a.bwd_ldx;
-    kp.bwd_scale = a.bwd_scale; kp.bwd_shift = a.bwd_shift; kp.bwd_mean = a.bwd_mean; kp.bwd_inv = a.bwd_inv; kp.bwd_stride = a.bwd_stride;
-    kp.bwd_slope = a.bwd_slope; kp.bwd_acc = a.bwd_acc; kp.bwd_reps = a.bwd_reps > 0 ? a.bwd_reps : 1;
-    kp.bwd_pg_tiles = a.bwd_pg > 0 ? (int)(a.bwd_pg / px_per_tile) : 0;
-    if (bwd_range) { kp.bwd_c0 = a.bwd_c0; kp.bwd_c = a.bwd_c; }
-    a.bwd_applied = 1;
-  }
-  if (take8) {
-    if (mode == 2 && a.pool2 && !a.mask && !a.stat_acc && !a.partials) {   // the pooled store: igemm8's 3x3 mode only
-      GI_REQUIRE(a.coffout == 0 && (int64_t)a.n * (a.Hs / 2) * (a.Ws / 2) * a.ldout < (1ll << 31), "igemm8: pooled output layout");
-      kp.pool = 1;
-      a.pool_applied = 1;
-    }
-    if (dual && !a.relu_in && a.mask && a.mask_bits && a.cout == 64 && !a.bias && a.act_out == GI_ACT_NONE && !a.stat_acc && !a.partials) kp.mask_bits = a.mask_bits;
-    if (kp.mask_bits && a.c1w_part && a.c1w_img && mtiles % 8 == 0 && a.c1w_part_floats >= (int64_t)grid * 1024 &&
-        (int64_t)a.n * 16 * a.Hs * a.Ws < (1ll << 31)) {
-      kp.c1w_img = a.c1w_img; kp.c1w_part = a.c1w_part; kp.c1w_scale = a.c1w_scale; kp.c1w_skip_out = a.c1w_skip_out;
-      a.c1w_applied = 1; a.c1w_blocks = grid;
-    }
-    GI_TRY(op_igemm8_launch(st, mode, dual, a.relu_in != 0, grid, kp, BN));
-    a.ntiles_out = mtiles * nph;
-    return GI_OK;
-  }
-  const int use6 = gi_opt(GI_OPT_IGEMM6);   // GI_IGEMM6=0: the first-generation halo kernels (also the fallback beyond 2^31-byte tensors)
-  if (use6 && mode != 2 && in_px * a.ldin * 2 < (1ll << 31) && (int64_t)a.cout * (mode == 1 ? 4 : 16) * a.cin * 2 * (dual ? 2 : 1) < (1ll << 31) &&
-      !(mode == 0 && a.relu_in)) {
-    const int lds6 = 2 * 320 * 128 + 4 * BNk * 128;
-    const int lds = lds6 > epi ? lds6 : epi;
-    const int v6 = (dual ? 4 : (BN == 64 ? 2 : 0) + mode) * 2 + (a.relu_in ? 1 : 0);
-    static GiDevOnce attr6[10];
-#define GI_K6(MODE_, BN_, RELU_) do { \
-      if (attr6[v6].first()) { GI_HIP(hipFuncSetAttribute((const void*)igemm6_kernel<MODE_, BN_, RELU_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); } \
-      hipLaunchKernelGGL((igemm6_kernel<MODE_, BN_, RELU_>), dim3(grid), dim3(512), lds, st, kp); } while (0)
+  GI_TRY(fill_halo_args(kp, p, a));
+  const dim3 grid(p.grid);
+#define GI_K5(V, MODE_, BN_, NAME) case V: return gi_launch_lds<igemm5_kernel<MODE_, BN_>>(grid, 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
+#define GI_K6(V, MODE_, BN_, RELU_, NAME) case V: return gi_launch_lds<igemm6_kernel<MODE_, BN_, RELU_>>(grid, 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
+  // (igemm5, igemm6, igemm5<3,128>: the order the kernels have always been instantiated in, i.e. their order in the code object)
+  if (p.family == GI_FAM_IGEMM5 && p.variant < 6) switch (p.variant) { GI_IGEMM5_KERNELS(GI_K5) }
+  if (p.family == GI_FAM_IGEMM6) {
 #ifdef GI_ABLATION   // timing-only ablation kernels compute wrong results: compiled only with `build.sh -DGI_ABLATION`
-    { const char* e = getenv("GI_IGEMM6_DBG"); const int dbg = e ? atoi(e) : 0;
-      if (dbg && v6 == 3) {
-#define GI_K6D(D_) do { GI_HIP(hipFuncSetAttribute((const void*)igemm6_kernel<1, 128, true, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((igemm6_kernel<1, 128, true, D_>), dim3(grid), dim3(512), lds, st, kp); } while (0)
-        switch (dbg) {
-          case 1: GI_K6D(1); break; case 2: GI_K6D(2); break; case 4: GI_K6D(4); break; case 8: GI_K6D(8); break;
-          case 16: GI_K6D(16); break; case 3: GI_K6D(3); break; case 5: GI_K6D(5); break; case 6: GI_K6D(6); break;
-          case 7: GI_K6D(7); break; case 23: GI_K6D(23); break; case 32: GI_K6D(32); break; case 39: GI_K6D(39); break;
-          case 64: GI_K6D(64); break; case 96: GI_K6D(96); break; case 225: GI_K6D(225); break; case 231: GI_K6D(231); break; default: GI_K6D(9); break;
-        }
-#undef GI_K6D
-        GI_LAUNCH_CHECK();
-        a.ntiles_out = mtiles * nph;
-        return GI_OK;
-      } }
-#endif
-    switch (v6) {
-      case 0: GI_K6(0, 128, false); gi_note_kernel("igemm6<0,128>"); break;
-      case 2: GI_K6(1, 128, false); gi_note_kernel("igemm6<1,128>"); break;
-      case 3: GI_K6(1, 128, true); gi_note_kernel("igemm6<1,128,relu>"); break;
-      case 4: GI_K6(0, 64, false); gi_note_kernel("igemm6<0,64>"); break;
-      case 6: GI_K6(1, 64, false); gi_note_kernel("igemm6<1,64>"); break;
-      case 7: GI_K6(1, 64, true); gi_note_kernel("igemm6<1,64,relu>"); break;
-      case 8: GI_K6(3, 128, false); gi_note_kernel("igemm6<3,128>"); break;
-      default: GI_K6(3, 128, true); gi_note_kernel("igemm6<3,128,relu>"); break;
+    const char* e = getenv("GI_IGEMM6_DBG"); const int dbg = e ? atoi(e) : 0;
+#define GI_K6D(D_) case D_: return gi_launch_lds<igemm6_kernel<1, 128, true, D_>>(grid, 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
+    if (dbg && p.variant == 3) switch (dbg) {
+      GI_K6D(1) GI_K6D(2) GI_K6D(4) GI_K6D(8) GI_K6D(16) GI_K6D(3) GI_K6D(5) GI_K6D(6) GI_K6D(7) GI_K6D(23) GI_K6D(32) GI_K6D(39)
+      GI_K6D(64) GI_K6D(96) GI_K6D(225) GI_K6D(231)
+      default: return gi_launch_lds<igemm6_kernel<1, 128, true, 9>>(grid, 512, p.lds_bytes, p.lds_attr_bytes, st, kp);
     }
+#undef GI_K6D
+#endif
+    switch (p.variant) { GI_IGEMM6_KERNELS(GI_K6) }
+  }
+  switch (p.variant) { GI_IGEMM5_DUAL_KERNEL(GI_K5) }
+#undef GI_K5
 #undef GI_K6
-    GI_LAUNCH_CHECK();
-    a.ntiles_out = mtiles * nph;
-    return GI_OK;
-  }
-  if (dual) {
-    static GiDevOnce attr_dual;
-    if (attr_dual.first()) { GI_HIP(hipFuncSetAttribute((const void*)igemm5_kernel<3, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
-    hipLaunchKernelGGL((igemm5_kernel<3, 128>), dim3(grid), dim3(512), LDS, st, kp);
-    gi_note_kernel("igemm5<3,128>");
-    GI_LAUNCH_CHECK();
-    a.ntiles_out = mtiles * nph;
-    return GI_OK;
-  }
-  const int vi = (BN == 64 ? 3 : 0) + mode;
-  if (attr[vi].first()) { GI_HIP(hipFuncSetAttribute(fn[vi], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
-  switch (vi) {
-    case 0: hipLaunchKernelGGL((igemm5_kernel<0, 128>), dim3(grid), dim3(512), LDS, st, kp); break;
-    case 1: hipLaunchKernelGGL((igemm5_kernel<1, 128>), dim3(grid), dim3(512), LDS, st, kp); break;
-    case 2: hipLaunchKernelGGL((igemm5_kernel<2, 128>), dim3(grid), dim3(512), LDS, st, kp); break;
-    case 3: hipLaunchKernelGGL((igemm5_kernel<0, 64>), dim3(grid), dim3(512), LDS, st, kp); break;
-    case 4: hipLaunchKernelGGL((igemm5_kernel<1, 64>), dim3(grid), dim3(512), LDS, st, kp); break;
-    default: hipLaunchKernelGGL((igemm5_kernel<2, 64>), dim3(grid), dim3(512), LDS, st, kp); break;
-  }
-  { static const char* nm[6] = {"igemm5<0,128>", "igemm5<1,128>", "igemm5<2,128>", "igemm5<0,64>", "igemm5<1,64>", "igemm5<2,64>"}; gi_note_kernel(nm[vi]); }
-  GI_LAUNCH_CHECK();
-  a.ntiles_out = mtiles * nph;
-  return GI_OK;
+  return GI_ERR_INVALID;
 }

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "stat_acc.h"
 #include "bn_acc.h"
+#include "igemm_plan.h"
 
 namespace {
 
@@ -439,7 +440,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) igemm7_kernel(KP7 p)
   }
   constexpr int CPRO = BN / 8;   // 16-byte chunks per output row
   const int oc = tid % CPRO;
-  if (NW != 4 || !p.fold) {      // (the folded normalisation below is the four-wave kernel's: op_igemm7 never asks the other for it)
+  if (NW != 4 || !p.fold) {      // (the folded normalisation below is the four-wave kernel's: the plan never asks the other for it)
 #pragma unroll 1
     for (int r = tid / CPRO; r < BM; r += NTHR / CPRO) {
       const int m = m0 + r;
@@ -550,74 +551,38 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) igemm7_kernel(KP7 p)
   }
 }
 
+template <int NS, int PF, int NW>
+int launch7(hipStream_t st, const IgemmPlan& p, const KP7& kp) {
+#define GI_K7(V, PHASE_, BN_, NAME) case V: return gi_launch_lds<igemm7_kernel<PHASE_, BN_, NS, PF, NW>>(dim3(p.grid), NW * 64, p.lds_bytes, p.lds_attr_bytes, st, kp);
+  switch (p.variant) { GI_IGEMM7_KERNELS(GI_K7) }
+#undef GI_K7
+  return GI_ERR_INVALID;
+}
+
 }  // namespace
 
-const char* gi_igemm3_zero_page(int dev);   // igemm3.hip
-
-// modes 0 (Conv2d 4x4/s2/p1 gather) and 1 (sub-pixel phases), fp16, layers with fewer than 256 tiles of 128 x 128.
-// Returns GI_ERR_UNSUPPORTED for what it does not serve (the caller falls back to igemm.hip).
-int op_igemm7(hipStream_t st, int mode, IgemmArgs& a) {
-  if (mode != 0 && mode != 1) return GI_ERR_UNSUPPORTED;
-  if (a.cin % 64 != 0 || a.cout % 64 != 0 || a.force_splitk != 0) return GI_ERR_UNSUPPORTED;
-  if (!gi_opt(GI_OPT_IGEMM7)) return GI_ERR_UNSUPPORTED;   // GI_IGEMM7=0: igemm.hip serves these layers
-  int max_split = gi_tune("GI_IGEMM7_MAXSPLIT", 8);   // (measured: d7 20.6 us with 16 splits, 18.6 us with 8: the last arriver's tail)
-  if (max_split < 1) max_split = 8;
-  const int M = a.n * a.Hs * a.Ws;
-  const int nph = mode == 1 ? 4 : 1;
-  const int mtiles = (M + 127) / 128;
-  int BN = (a.cout % 128 == 0 && mtiles * (a.cout / 128) * nph >= 64) ? 128 : 64;
-  {   // GI_IGEMM7_BN (ablation build): force the N tile
-    const int force_bn = gi_tune("GI_IGEMM7_BN", 0);
-    if (force_bn == 64 || (force_bn == 128 && a.cout % 128 == 0)) BN = force_bn;
-  }
-  const int ntiles = a.cout / BN;
-  const int tiles = mtiles * ntiles * nph;
-  const int Ktot = (mode == 1 ? 4 : 16) * a.cin, nk = Ktot / 64;
-  int splitk = (256 + tiles - 1) / tiles;
-  if (splitk > max_split) splitk = max_split;
-  if (splitk > nk / 8) splitk = nk / 8;   // at least 8 K tiles per split (u7: 21.7 us with 4 tiles per split, 17.9 us with 8)
-  if (splitk < 1) splitk = 1;
-  int kps = (nk + splitk - 1) / splitk;
-  splitk = (nk + kps - 1) / kps;
-  if (splitk > 1 && (!a.tickets || !a.ws || tiles > GI_IGEMM_TICKETS || a.ws_bytes < (int64_t)splitk * tiles * 128 * BN * 4)) return GI_ERR_UNSUPPORTED;
-  // Folded normalisation (IgemmFold): taken when ONE workgroup can normalise a channel column in about the time the separate pass
-  // spends before its first byte moves (a dependent launch + the accumulator reads: ~5 us): the column finisher reads and writes
-  // out_pixels x BN halves at 60 - 100 GB/s (one CU, other workgroups' rows: guides/MI355X_MICROARCH.md "handoff-payload"), i.e.
-  // ~1.5 us per 64 KiB each way. The column tickets are the last 32 of the GI_IGEMM_TICKETS words.
-  constexpr int COL_TICKETS = 32;
-  const int64_t out_pixels = (int64_t)M * nph;
-  const int64_t col_bytes = out_pixels * BN * 2;
-  const bool fold = a.fold && gi_opt(GI_OPT_BN_FOLD) && a.stat_acc && a.fold->bn.groups == 1 && a.fold->bn.acc == a.stat_acc && a.tickets &&
-                    ntiles <= COL_TICKETS && tiles <= GI_IGEMM_TICKETS - COL_TICKETS && col_bytes <= (int64_t)gi_tune("GI_FOLD_MAX_KB", 256) * 1024 &&
-                    out_pixels * a.ldout * 2 < (1ll << 31) && out_pixels * a.fold->lddst * 2 < (1ll << 31) && a.ldout % 8 == 0 && a.coffout % 8 == 0 &&
-                    a.fold->lddst % 8 == 0 && a.fold->coffdst % 8 == 0 && (a.fold->act == GI_ACT_RELU || a.fold->act == GI_ACT_LRELU || a.fold->act == GI_ACT_NONE);
-  int dev = 0;
-  GI_HIP(hipGetDevice(&dev));
-  const char* zero = gi_igemm3_zero_page(dev);
-  if (!zero) return GI_ERR_HIP;
+// modes 0 (Conv2d 4x4/s2/p1 gather) and 1 (sub-pixel phases), fp16, layers with fewer than 256 tiles of 128 x 128
+int launch_igemm7(hipStream_t st, const IgemmPlan& p, const IgemmArgs& a) {
+  constexpr int COL_TICKETS = 32;   // the column tickets of the folded normalisation: the last 32 of the GI_IGEMM_TICKETS words
+  const int mode = p.mode;
   KP7 kp;
-  kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out; kp.zero = zero;
+  kp.in = (const char*)a.in; kp.w = (const char*)a.w; kp.out = (char*)a.out; kp.zero = gi_igemm_zero_page();
+  if (!kp.zero) { gi_set_error("igemm7: no zero page"); return GI_ERR_HIP; }
   kp.bias = a.bias; kp.partials = a.stat_acc ? nullptr : a.partials;
   kp.stat_acc = a.stat_acc; kp.stat_pg = a.stat_pg; kp.stat_reps = a.stat_reps > 0 ? a.stat_reps : 1;
-  a.stat_used = a.stat_acc ? 1 : 0;
-  GI_REQUIRE(!a.stat_acc || a.stat_pg == 0 || a.stat_pg % 128 == 0, "igemm7: stat_pg=%d must be a multiple of 128", a.stat_pg);
   kp.ws = a.ws; kp.tickets = a.tickets;
-  kp.M = M; kp.Hs = a.Hs; kp.Ws = a.Ws;
+  kp.M = a.n * a.Hs * a.Ws; kp.Hs = a.Hs; kp.Ws = a.Ws;
   kp.cin = a.cin; kp.ldin = a.ldin; kp.coffin = a.coffin;
   kp.cout = a.cout; kp.ldout = a.ldout; kp.coffout = a.coffout;
-  kp.Ktot = Ktot; kp.nk = nk; kp.splitk = splitk; kp.kt_per_split = kps;
+  kp.Ktot = (mode == 1 ? 4 : 16) * a.cin; kp.nk = kp.Ktot / 64; kp.splitk = p.splitk; kp.kt_per_split = p.kt_per_split;
   kp.relu_in = a.relu_in; kp.act_out = a.act_out;
   kp.relu_cend = a.relu_cend > 0 ? a.relu_cend : a.cin;
   if (mode == 1) { kp.Hin = a.Hs; kp.Win = a.Ws; kp.Hout = 2 * a.Hs; kp.Wout = 2 * a.Ws; }
   else { kp.Hin = 2 * a.Hs; kp.Win = 2 * a.Ws; kp.Hout = a.Hs; kp.Wout = a.Ws; }
-  GI_REQUIRE((int64_t)a.n * kp.Hin * kp.Win * a.ldin < (1ll << 31) && (int64_t)a.n * kp.Hout * kp.Wout * a.ldout < (1ll << 31),
-             "igemm7: tensor too large for 32-bit offsets");
-  kp.mtiles = mtiles; kp.ntiles = ntiles;
+  kp.mtiles = p.mtiles; kp.ntiles = p.ntiles;
   kp.dbg = gi_tune("GI_IGEMM7_DBG", 0);
-  kp.fold = fold ? 1 : 0;
-  a.fold_applied = kp.fold;
-  if (fold) {
-    gi_note_fold();
+  kp.fold = p.fold ? 1 : 0;
+  if (p.fold) {
     const IgemmFold& f = *a.fold;
     gi_fill_acc_params(kp.fa, f.bn);
     kp.col_tickets = a.tickets + (GI_IGEMM_TICKETS - COL_TICKETS);
@@ -628,56 +593,10 @@ int op_igemm7(hipStream_t st, int mode, IgemmArgs& a) {
     kp.col_tickets = nullptr; kp.fa = BnAccP{}; kp.fdst = nullptr; kp.flddst = kp.fcoffdst = kp.fact = 0;
     kp.fdrop = nullptr; kp.fdrop_scale = 1.f; kp.fdrop_seed = 0; kp.fdrop_thresh = 0;
   }
-  const int nyz = ntiles * nph * splitk;
-  const int grid = mtiles >= 8 ? ((mtiles + 7) / 8) * 8 * nyz : mtiles * nyz;
-  // shipped choice, measured on d5 / d6 / d7 / u7 / u6 at the headline batch (tools/r4_small.sh, profiles/r04_igemm7_variants.txt):
-  // four stages and one split per tail iteration. A six-stage ring on the 64-column tiles (four K tiles in flight) ran 3 - 5 us
-  // SLOWER per layer (the five-tile prologue burst of every CU delays the first tile by more than the deeper ring gains), two or
-  // four splits of the tail in flight changed nothing (+-0.5 us): the tail's round trips are not what these launches wait for.
-  constexpr int GI7_NSTG = 4, GI7_PF = 1;
-  int nstg = GI7_NSTG, pf = GI7_PF;
-#ifdef GI_ABLATION
-  nstg = gi_tune("GI_IGEMM7_NSTG", GI7_NSTG);
-  pf = gi_tune("GI_IGEMM7_PF", GI7_PF);
-  if (BN == 128 || nstg != 6) nstg = 4;
-  if (pf != 2 && pf != 4) pf = 1;
+  if (p.nw == 8) return launch7<4, 1, 8>(st, p, kp);
+#ifdef GI_ABLATION   // ring stages / tail prefetch of the four-wave kernel (GI_IGEMM7_NSTG, GI_IGEMM7_PF)
+  if (p.nstg == 6) return p.pf == 4 ? launch7<6, 4, 4>(st, p, kp) : p.pf == 2 ? launch7<6, 2, 4>(st, p, kp) : launch7<6, 1, 4>(st, p, kp);
+  if (p.pf != 1) return p.pf == 4 ? launch7<4, 4, 4>(st, p, kp) : launch7<4, 2, 4>(st, p, kp);
 #endif
-  // waves per workgroup (kernel header): eight unless the folded normalisation is asked for (the four-wave kernel's) or GI_IGEMM7_WAVES=4
-  const int nw = (fold || gi_opt(GI_OPT_IGEMM7_WAVES) == 4) ? 4 : 8;
-  const int ring = nstg * (128 + BN) * 128, epi = 128 * (BN + 8) * 2 + 4 * BN * 8;
-  const int LDS = ring > epi ? ring : epi;
-  const int vi = (BN == 64 ? 2 : 0) + mode;
-  auto launch = [&](auto NS, auto PFc, auto NWc) -> int {
-    constexpr int ns = decltype(NS)::value, pfc = decltype(PFc)::value, nwc = decltype(NWc)::value;
-    static GiDevOnce attr_set[4];
-    const void* fn[4] = {(const void*)igemm7_kernel<0, 128, ns, pfc, nwc>, (const void*)igemm7_kernel<1, 128, ns, pfc, nwc>,
-                         (const void*)igemm7_kernel<0, 64, ns, pfc, nwc>, (const void*)igemm7_kernel<1, 64, ns, pfc, nwc>};
-    if (attr_set[vi].first()) { GI_HIP(hipFuncSetAttribute(fn[vi], hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024)); }
-    switch (vi) {
-      case 0: hipLaunchKernelGGL((igemm7_kernel<0, 128, ns, pfc, nwc>), dim3(grid), dim3(nwc * 64), LDS, st, kp); break;
-      case 1: hipLaunchKernelGGL((igemm7_kernel<1, 128, ns, pfc, nwc>), dim3(grid), dim3(nwc * 64), LDS, st, kp); break;
-      case 2: hipLaunchKernelGGL((igemm7_kernel<0, 64, ns, pfc, nwc>), dim3(grid), dim3(nwc * 64), LDS, st, kp); break;
-      default: hipLaunchKernelGGL((igemm7_kernel<1, 64, ns, pfc, nwc>), dim3(grid), dim3(nwc * 64), LDS, st, kp); break;
-    }
-    return GI_OK;
-  };
-  using I1_ = std::integral_constant<int, 1>;
-  using I2_ = std::integral_constant<int, 2>;
-  using I4_ = std::integral_constant<int, 4>;
-  using I6_ = std::integral_constant<int, 6>;
-  using I8_ = std::integral_constant<int, 8>;
-#ifdef GI_ABLATION
-  if (nw == 8) GI_TRY(launch(I4_{}, I1_{}, I8_{}));
-  else if (nstg == 6) { if (pf == 4) GI_TRY(launch(I6_{}, I4_{}, I4_{})); else if (pf == 2) GI_TRY(launch(I6_{}, I2_{}, I4_{})); else GI_TRY(launch(I6_{}, I1_{}, I4_{})); }
-  else { if (pf == 4) GI_TRY(launch(I4_{}, I4_{}, I4_{})); else if (pf == 2) GI_TRY(launch(I4_{}, I2_{}, I4_{})); else GI_TRY(launch(I4_{}, I1_{}, I4_{})); }
-#else
-  (void)nstg; (void)pf;
-  if (nw == 8) GI_TRY(launch(std::integral_constant<int, GI7_NSTG>{}, std::integral_constant<int, GI7_PF>{}, I8_{}));
-  else GI_TRY(launch(std::integral_constant<int, GI7_NSTG>{}, std::integral_constant<int, GI7_PF>{}, I4_{}));
-#endif
-  { static const char* nm[8] = {"igemm7<0,128>", "igemm7<1,128>", "igemm7<0,64>", "igemm7<1,64>",
-                                "igemm7<0,128>+bn", "igemm7<1,128>+bn", "igemm7<0,64>+bn", "igemm7<1,64>+bn"}; gi_note_kernel(nm[vi + (fold ? 4 : 0)]); }
-  GI_LAUNCH_CHECK();
-  a.ntiles_out = mtiles * nph;
-  return GI_OK;
+  return launch7<4, 1, 4>(st, p, kp);
 }

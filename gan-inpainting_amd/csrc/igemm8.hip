@@ -752,63 +752,31 @@ __global__ void __launch_bounds__(256, 2) igemm8_kernel(KP5 p) {
 
 }  // namespace
 
-// Launched by op_igemm5 (igemm5.hip) with the kernel arguments it has prepared; grid as igemm6's.
-int op_igemm8_launch(hipStream_t st, int mode, bool dual, bool relu, int grid, const KP5& kp, int bn) {
-  if (mode == 2 && bn == 64) {      // VGG conv1_2: 64 output channels
-    // (64-column tiles were also measured on the 4-tap layers whose 128-column grid is one workgroup per CU - d3, u4, critic conv4:
-    //  twice the workgroups, two per CU - and ran 6 - 10 % SLOWER than igemm6 there: twice the halo DMA per MAC; not instantiated)
-    static GiDevOnce attr64;
-    const int lds64 = 2 * 22528 + 4 * 4096;
-    if (attr64.first()) { GI_HIP(hipFuncSetAttribute((const void*)igemm8_kernel<2, false, 0, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds64)); }
-    hipLaunchKernelGGL((igemm8_kernel<2, false, 0, 64>), dim3(grid), dim3(256), lds64, st, kp);
-    gi_note_kernel("igemm8<2,64>");
-    GI_LAUNCH_CHECK();
-    return GI_OK;
-  }
-  const int LDS = (mode == 2 ? 2 * 22528 : 2 * 20480) + 4 * 8192;   // 4-tap modes: = the epilogue's 256 x 136 halves + 4 x 128 x 2 floats
-  static GiDevOnce attr[8];
-  const int v = mode == 2 ? 6 : (dual ? 2 : mode) * 2 + (relu ? 1 : 0);
-#define GI_K8(MODE_, RELU_, NAME_) do { \
-    if (attr[v].first()) { GI_HIP(hipFuncSetAttribute((const void*)igemm8_kernel<MODE_, RELU_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); } \
-    hipLaunchKernelGGL((igemm8_kernel<MODE_, RELU_>), dim3(grid), dim3(256), LDS, st, kp); gi_note_kernel(NAME_); } while (0)
+// grid as igemm6's; the kernel table is in igemm_plan.h
+// (64-column tiles were also measured on the 4-tap layers whose 128-column grid is one workgroup per CU - d3, u4, critic conv4:
+//  twice the workgroups, two per CU - and ran 6 - 10 % SLOWER than igemm6 there: twice the halo DMA per MAC; not instantiated)
+int launch_igemm8(hipStream_t st, const IgemmPlan& p, const IgemmArgs& a) {
+  KP5 kp;
+  GI_TRY(fill_halo_args(kp, p, a));
+  const dim3 grid(p.grid);
+#define GI_K8(V, MODE_, RELU_, BN_, NAME) case V: return gi_launch_lds<igemm8_kernel<MODE_, RELU_, 0, BN_>>(grid, 256, p.lds_bytes, p.lds_attr_bytes, st, kp);
 #ifdef GI_ABLATION   // timing-only ablation kernels compute wrong results: compiled only with `build.sh -DGI_ABLATION`
-  { const char* e = getenv("GI_IGEMM8_DBG"); const int dbg = e ? atoi(e) : 0;
-    if (dbg && v == 3) {
-#define GI_K8D(D_) do { GI_HIP(hipFuncSetAttribute((const void*)igemm8_kernel<1, true, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-      hipLaunchKernelGGL((igemm8_kernel<1, true, D_>), dim3(grid), dim3(256), LDS, st, kp); } while (0)
-      switch (dbg) {
-        case 1: GI_K8D(1); break; case 2: GI_K8D(2); break; case 4: GI_K8D(4); break; case 8: GI_K8D(8); break; case 16: GI_K8D(16); break;
-        case 32: GI_K8D(32); break; case 5: GI_K8D(5); break; case 7: GI_K8D(7); break; case 6: GI_K8D(6); break; case 3: GI_K8D(3); break;
-        case 39: GI_K8D(39); break; case 13: GI_K8D(13); break; default: GI_K8D(15); break;
-      }
-#undef GI_K8D
-      GI_LAUNCH_CHECK();
-      return GI_OK;
-    }
-    // the gather mode (stride-2 convolution: the critic's conv2, the generator's d2), GI_IGEMM8_DBG0
-    const char* e0 = getenv("GI_IGEMM8_DBG0"); const int dbg0 = e0 ? atoi(e0) : 0;
-    if (dbg0 && v == 0) {
-#define GI_K8D0(D_) do { GI_HIP(hipFuncSetAttribute((const void*)igemm8_kernel<0, false, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-      hipLaunchKernelGGL((igemm8_kernel<0, false, D_>), dim3(grid), dim3(256), LDS, st, kp); } while (0)
-      switch (dbg0) {
-        case 1: GI_K8D0(1); break; case 2: GI_K8D0(2); break; case 4: GI_K8D0(4); break; case 16: GI_K8D0(16); break; case 32: GI_K8D0(32); break;
-        case 5: GI_K8D0(5); break; case 7: GI_K8D0(7); break; default: GI_K8D0(39); break;
-      }
-#undef GI_K8D0
-      GI_LAUNCH_CHECK();
-      return GI_OK;
-    } }
-#endif
-  switch (v) {
-    case 0: GI_K8(0, false, "igemm8<0>"); break;
-    case 1: GI_K8(0, true, "igemm8<0,relu>"); break;
-    case 2: GI_K8(1, false, "igemm8<1>"); break;
-    case 3: GI_K8(1, true, "igemm8<1,relu>"); break;
-    case 4: GI_K8(3, false, "igemm8<3>"); break;
-    case 5: GI_K8(3, true, "igemm8<3,relu>"); break;
-    default: GI_K8(2, false, "igemm8<2>"); break;
+  const char* e = getenv("GI_IGEMM8_DBG"); const int dbg = e ? atoi(e) : 0;
+#define GI_K8D(M_, R_, D_) case D_: return gi_launch_lds<igemm8_kernel<M_, R_, D_>>(grid, 256, p.lds_bytes, p.lds_attr_bytes, st, kp);
+  if (dbg && p.variant == 3) switch (dbg) {
+    GI_K8D(1, true, 1) GI_K8D(1, true, 2) GI_K8D(1, true, 4) GI_K8D(1, true, 8) GI_K8D(1, true, 16) GI_K8D(1, true, 32) GI_K8D(1, true, 5)
+    GI_K8D(1, true, 7) GI_K8D(1, true, 6) GI_K8D(1, true, 3) GI_K8D(1, true, 39) GI_K8D(1, true, 13)
+    default: return gi_launch_lds<igemm8_kernel<1, true, 15>>(grid, 256, p.lds_bytes, p.lds_attr_bytes, st, kp);
   }
+  // the gather mode (stride-2 convolution: the critic's conv2, the generator's d2), GI_IGEMM8_DBG0
+  const char* e0 = getenv("GI_IGEMM8_DBG0"); const int dbg0 = e0 ? atoi(e0) : 0;
+  if (dbg0 && p.variant == 0) switch (dbg0) {
+    GI_K8D(0, false, 1) GI_K8D(0, false, 2) GI_K8D(0, false, 4) GI_K8D(0, false, 16) GI_K8D(0, false, 32) GI_K8D(0, false, 5) GI_K8D(0, false, 7)
+    default: return gi_launch_lds<igemm8_kernel<0, false, 39>>(grid, 256, p.lds_bytes, p.lds_attr_bytes, st, kp);
+  }
+#undef GI_K8D
+#endif
+  switch (p.variant) { GI_IGEMM8_KERNELS(GI_K8) }
 #undef GI_K8
-  GI_LAUNCH_CHECK();
-  return GI_OK;
+  return GI_ERR_INVALID;
 }

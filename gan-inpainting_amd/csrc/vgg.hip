@@ -19,8 +19,6 @@
 
 #include "common.h"
 
-int op_igemm3(hipStream_t st, int mode, IgemmArgs& a);
-
 namespace {
 
 constexpr int NCONV = 13;
@@ -767,7 +765,7 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
       // the pooled layers (conv1_2, conv2_2, conv3_4, conv4_4) are never taps: where the kernel can, it stores the 2x2 max pool of
       // its tile and the full-resolution map is never written
       a.pool2 = (!grad && kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
-      GI_TRY(op_igemm3(st, 2, a));
+      GI_TRY(op_igemm(st, GI_F16, 2, a));
       cur ^= 1;
       curp = outp;
       pooled = a.pool_applied != 0;
@@ -907,7 +905,7 @@ int vgg_backward(gi_vgg* v, int n, int stop, float* layer_out, float* grad_out, 
       a.mask = v->ga[below]; a.ldmask = kCin[l]; a.coffmask = 0; a.mask_slope = 0.f;
       a.add = seed_of(below); a.ldadd = kCin[l]; a.coffadd = 0;
     }
-    GI_TRY(op_igemm3(st, 2, a));
+    GI_TRY(op_igemm(st, GI_F16, 2, a));
     if (pool) {
       GI_TRY(act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
     } else {

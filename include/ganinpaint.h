@@ -499,6 +499,20 @@ int gi_conv_s2_forward_ex(gi_ctx* ctx, int dtype, const void* in, const void* w_
 int gi_convT_s2_forward_ex(gi_ctx* ctx, int dtype, const void* in, const void* w_phase, void* out,
                            int n, int H, int W, int ca, int ldin, int cb, int ldout, int relu_in,
                            int act_out, float* ws, int64_t ws_bytes, gi_igemm_ex* ex);
+/* Which kernel the two entries above (mode 0 / 1) or a 3x3 / s1 VGG convolution (mode 2) would launch for a layer, without launching
+ * it: the same decision function on the same arguments, host arithmetic only - no HIP call, works without a GPU. n, Hs, Ws: the small
+ * grid (mode 0: the output, H / 2 x W / 2); ws_bytes > 0: a workspace of that size is passed, has_tickets: and the split-K ticket
+ * counters; ex as above (pointers are only tested for null; may be null); offered: what the networks can add to a launch -
+ * 1 the folded normalisation (with ex->stat_acc), 2 the first layer's weight gradient (with ex->mask_bits), 4 the pooled store,
+ * 8 a bias. Returns as the entries do (GI_ERR_INVALID with gi_last_error set; mode 2: GI_ERR_UNSUPPORTED when no kernel serves it). */
+typedef struct gi_igemm_plan_info {
+  char name[48];                 /* what gi_debug_last_kernel would say after the launch */
+  int grid, splitk, ntiles_out;  /* workgroups, K splits */
+  int mask_applied, bwd_applied, stat_used, c1w_applied, c1w_blocks, pool_applied, fold_applied;
+} gi_igemm_plan_info;
+int gi_debug_igemm_plan(int dtype, int mode, int n, int Hs, int Ws, int cin, int ldin, int cout, int ldout, int relu_in,
+                        int act_out, int64_t ws_bytes, int has_tickets, const gi_igemm_ex* ex, int offered,
+                        gi_igemm_plan_info* out);
 /* exact accumulator blocks (csrc/stat_acc.h): words per block of c channels; totals of the two quantities of a population
  * as doubles, out_dev[2][c] (device) */
 int64_t gi_stat_acc_words(int c);
