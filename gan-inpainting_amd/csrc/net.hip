@@ -695,15 +695,20 @@ BNPtrs bn_ptrs(const gi_net* net, int slot, const BN& b, int group = 0) {
   return {base, base + b.c, base + 2 * b.c, base + 3 * b.c};
 }
 
-// raw (pixels,c) conv output with per-tile partial statistics -> normalise + activation into dst.
-// With bn_groups = g the batch is g consecutive groups of pixels/g pixels, each normalised with its OWN batch
-// statistics (the reference calls the critic separately on the real and on the fake batch: two BatchNorm
-// populations, running statistics updated group by group in that order).
-// apply = false: statistics / scale / shift only (a consumer applies the affine map itself, C1Affine)
+// Channels [coff, coff + c) of an NHWC tensor whose pixels are ld elements apart (ld omitted: dense, ld = c)
+struct Slice { const void* p = nullptr; int c = 0, ld = 0, coff = 0; };
+Slice sl(const void* p, int c, int ld = 0, int coff = 0) { return {p, c, ld ? ld : c, coff}; }
+// the generator's concat buffer of level k (gi_net::oC) and its halves; the input of up-convolution k
+void* concat_buf(const gi_net* net, int s, int k) { return net->slot(s, net->oC[k]); }
+Slice concat(const gi_net* net, int s, int k) { return sl(concat_buf(net, s, k), 2 * net->ch[k]); }
+Slice skip_half(const gi_net* net, int s, int k) { return sl(concat_buf(net, s, k), net->ch[k], 2 * net->ch[k], 0); }
+Slice up_half(const gi_net* net, int s, int k) { return sl(concat_buf(net, s, k), net->ch[k], 2 * net->ch[k], net->ch[k]); }
+Slice up_input(const gi_net* net, int s, int k) { return k == net->nd ? sl(net->slot(s, net->oE), net->ch[k]) : concat(net, s, k); }
+
 // Statistics plan of one BatchNorm layer, fixed BEFORE its GEMM runs: with `use` the GEMM adds its tile sums to the
 // layer's exact accumulators (IgemmArgs::stat_acc) and bn_forward needs no reduction launch.
 struct StatPlan { unsigned long long* acc = nullptr; unsigned long long* zero_next = nullptr; int zero_words = 0; int pg = 0; int reps = 1; bool use = false; };
-// (`use` is cleared by the igemm wrapper when the kernel that ran put its statistics into partial rows instead)
+// (`use` is cleared by gemm_run when the kernel that ran put its statistics into partial rows instead)
 // replicas for `adders` tiles adding to one block: about 256 requests per 64-byte line (~3 us of queueing at the atomic unit)
 int stat_reps_for(int64_t adders) {
   int r = 1;
@@ -746,21 +751,62 @@ void bn_acc_commit(gi_net* net, int slot, const BN& b, const StatPlan& sp) {
   if (b.id >= 0) net->eval_gen[slot][b.id] = 0;
 }
 
-// drop_p > 0 with the accumulator path: the keep-mask is drawn inside the normalisation pass (seed drop_seed) and
-// stored at `drop`; otherwise `drop` (if any) is read.
-int bn_forward(gi_net* net, int slot, const BN& b, const void* raw, int64_t pixels, int ntiles, void* dst, int ldy,
-               int coffy, int act, const uint8_t* drop, float drop_scale, int train, bool apply = true,
-               const StatPlan* sp = nullptr, float drop_p = 0.f, uint64_t drop_seed = 0,
-               const void* side_src = nullptr, void* side_dst = nullptr, int64_t side_bytes = 0) {   // side copy: accumulator path only
+// Dropout of a decoder level as the pass that applies it sees it. p == 0: `mask` (if any) is read; p > 0: the keep-mask is drawn
+// inside that pass (same hash, same masks as op_fill_dropout) from `seed` and stored at `mask`.
+struct Dropout { uint8_t* mask = nullptr; float scale = 1.f; uint64_t seed = 0; float p = 0.f; };
+int dropout_draw(gi_net* net, Dropout& d, int64_t count) {
+  GI_TRY(op_fill_dropout(net->ctx->stream, d.mask, count, d.seed, d.p));
+  d.p = 0.f;
+  return GI_OK;
+}
+// The dropout of decoder level k in this forward (train mode, levels 5 .. nd - 1): an imposed mask is converted into the slot;
+// otherwise the next seed is taken and the mask drawn at once, or with `defer` left to the pass that applies it (Dropout::p > 0;
+// the BatchNorm generator calls dropout_draw itself where that pass turns out not to draw)
+int dropout_prepare(gi_net* net, int s, int k, int n, bool defer, Dropout& d) {
+  d = Dropout();
+  if (!net->train || !(net->dropout_p > 0.f) || k < 5 || k > net->nd - 1) return GI_OK;
+  const int co = net->ch[k - 1], hw = net->Hk[k - 1] * net->Wk[k - 1];
+  d.mask = (uint8_t*)net->slot(s, net->oMask[k]);
+  d.scale = 1.f / (1.f - net->dropout_p);
+  if (net->ext_mask[s][k]) return op_mask_nchw_to_nhwc(net->ctx->stream, net->ext_mask[s][k], d.mask, n, co, hw, 1);
+  d.seed = net->drop_seed + 0x1000003ull * (++net->drop_counter);
+  d.p = net->dropout_p;
+  return defer ? GI_OK : dropout_draw(net, d, (int64_t)n * hw * co);
+}
+
+// The copy of the input that the first layer's weight gradient reads (8.4 MB at the headline shape) rides in layer 2's
+// normalisation pass where that pass takes a side copy (bn_forward on the accumulator path, a multiple of 16 bytes);
+// input_copy is the device copy for every other case.
+struct SideCopy { const void* src = nullptr; void* dst = nullptr; int64_t bytes = 0; };
+SideCopy input_side_copy(const gi_net* net, int s, const float* x, int n, const StatPlan& sp) {
+  const int64_t bytes = (int64_t)n * net->H * net->W * 4;
+  if (!sp.use || bytes % 16 != 0) return SideCopy();
+  return {x, net->slot(s, net->oX), bytes};
+}
+int input_copy(gi_net* net, int s, const float* x, int n) {
+  GI_HIP(hipMemcpyAsync(net->slot(s, net->oX), x, (size_t)n * net->H * net->W * 4, hipMemcpyDeviceToDevice, net->ctx->stream));
+  return GI_OK;
+}
+
+// raw (pixels,c) conv output with per-tile partial statistics -> normalise + activation into dst.
+// With bn_groups = g the batch is g consecutive groups of pixels/g pixels, each normalised with its OWN batch
+// statistics (the reference calls the critic separately on the real and on the fake batch: two BatchNorm
+// populations, running statistics updated group by group in that order).
+// apply = false: statistics / scale / shift only (a consumer applies the affine map itself, C1Affine)
+// side: accumulator path only
+struct BnOpts { bool apply = true; Dropout drop; SideCopy side; };
+int bn_forward(gi_net* net, int slot, const BN& b, const void* raw, int64_t pixels, int ntiles, Slice dst, int act, int train,
+               const StatPlan& sp, const BnOpts& o = BnOpts()) {
   hipStream_t st = net->ctx->stream;
   const int g = net->kind == 1 ? net->bn_groups : 1;
   const int64_t pg = pixels / g;
   const size_t T = net->tsz();
-  if (sp && sp->use) {
-    const BnAccArgs a = bn_acc_args(net, slot, b, *sp, pg, g);
-    bn_acc_commit(net, slot, b, *sp);
-    if (apply) return op_bn_apply_acc(st, net->dtype, raw, dst, pixels, b.c, ldy, coffy, act, (uint8_t*)drop, drop_scale, drop_seed, drop_p, a,
-                                      side_src, side_dst, side_bytes);
+  const Dropout& drop = o.drop;
+  if (sp.use) {
+    const BnAccArgs a = bn_acc_args(net, slot, b, sp, pg, g);
+    bn_acc_commit(net, slot, b, sp);
+    if (o.apply) return op_bn_apply_acc(st, net->dtype, raw, (void*)dst.p, pixels, b.c, dst.ld, dst.coff, act, drop.mask, drop.scale, drop.seed, drop.p, a,
+                                        o.side.src, o.side.dst, o.side.bytes);
     return op_bn_finalize_acc(st, b.c, a);
   }
   // the GEMM epilogue's partial rows can be split between the groups when a group is a whole number of tiles
@@ -772,7 +818,7 @@ int bn_forward(gi_net* net, int slot, const BN& b, const void* raw, int64_t pixe
     GI_TRY(op_bn_finalize(st, (const float*)net->shared(net->oPart), rows, b.c, pg, net->params + b.gamma_off, net->params + b.beta_off,
                           net->buffers + b.rmean_off, net->buffers + b.rvar_off, p.scale, p.shift, p.mean, p.inv, train, 0.1f, 1e-5f, 2,
                           (int64_t)rows * 2 * b.c, 4 * b.c));
-    if (apply) GI_TRY(op_bn_apply(st, net->dtype, raw, dst, pixels, b.c, ldy, coffy, p.scale, p.shift, act, drop, drop_scale, pg, 4 * b.c));
+    if (o.apply) GI_TRY(op_bn_apply(st, net->dtype, raw, (void*)dst.p, pixels, b.c, dst.ld, dst.coff, p.scale, p.shift, act, drop.mask, drop.scale, pg, 4 * b.c));
     return GI_OK;
   }
   for (int j = 0; j < g; ++j) {
@@ -794,9 +840,9 @@ int bn_forward(gi_net* net, int slot, const BN& b, const void* raw, int64_t pixe
                             net->buffers + b.rvar_off, p.scale, p.shift, p.mean, p.inv, train, 0.1f, 1e-5f));
       if (b.id >= 0) net->eval_gen[slot][b.id] = (!train && g == 1) ? net->affine_gen : 0;
     }
-    if (apply)
-      GI_TRY(op_bn_apply(st, net->dtype, rj, (char*)dst + (int64_t)j * pg * ldy * T, pg, b.c, ldy, coffy, p.scale, p.shift, act,
-                         drop ? drop + (int64_t)j * pg * b.c : nullptr, drop_scale));
+    if (o.apply)
+      GI_TRY(op_bn_apply(st, net->dtype, rj, (char*)dst.p + (int64_t)j * pg * dst.ld * T, pg, b.c, dst.ld, dst.coff, p.scale, p.shift, act,
+                         drop.mask ? drop.mask + (int64_t)j * pg * b.c : nullptr, drop.scale));
   }
   return GI_OK;
 }
@@ -830,60 +876,95 @@ BwdFuse bwd_fuse_plan(gi_net* net, int slot, const BN& bn, const void* x, int64_
   f.slope = slope; f.pg = g == 2 ? pg : 0;
   return f;
 }
+// a reduction planned by an earlier, abandoned backward (a phase 1 without its phase 2) left sums in its accumulator block
+int clear_pending_bwd(gi_net* net, const BN* bn, int count) {
+  for (int i = 0; i < count; ++i) {
+    if (bn[i].c == 0 || bn[i].id < 0) continue;
+    BwdFuse& pend = net->bwd_pending[bn[i].id];
+    if (pend.planned) GI_HIP(hipMemsetAsync(pend.acc, 0, (size_t)bn[i].acc_block() * 8, net->ctx->stream));
+    pend = BwdFuse();
+  }
+  return GI_OK;
+}
 
-// IgemmArgs::c1w_* for the igemm() wrapper: the first layer's weight gradient from the second layer's input-gradient GEMM
+// IgemmArgs::c1w_*: the first layer's weight gradient from the second layer's input-gradient GEMM
 struct C1WFuse {
   const float* img = nullptr; float* part = nullptr; int64_t part_floats = 0; float scale = 1.f; int skip_out = 0;
   int applied = 0, blocks = 0;   // (returned)
 };
 
-// mask / ldmask / mask_slope / mask_applied: IgemmArgs::mask (activation backward fused into an input-gradient GEMM)
-int igemm(gi_net* net, int phase, const void* in, int cin, int ldin, int coffin, const void* w, void* out, int cout,
-          int ldout, int coffout, int n, int Hs, int Ws, int relu_in, int act_out, bool stats, int* ntiles, int relu_cend = 0,
-          const void* mask = nullptr, int ldmask = 0, float mask_slope = 0.f, int* mask_applied = nullptr,
-          const void* add = nullptr, int ldadd = 0, const float* bias = nullptr, StatPlan* sp = nullptr, BwdFuse* bf = nullptr,
-          const IgemmFold* fold = nullptr, int* fold_applied = nullptr, const unsigned long long* mask_bits = nullptr, C1WFuse* c1w = nullptr) {
+// One layer's implicit GEMM while it is assembled: gemm_args() fills what the net owns and what every call needs, the call site
+// sets the optional IgemmArgs fields it uses by name (bias, relu_in, relu_cend, act_out), the with_*() functions attach the fused
+// passes, gemm_run() launches and copies what the kernel reports back into the attached plans. Everything else stays zero.
+struct Gemm {
   IgemmArgs a;
+  StatPlan* sp = nullptr; BwdFuse* bf = nullptr; C1WFuse* c1w = nullptr;
+};
+Gemm gemm_args(const gi_net* net, Slice in, const void* w, Slice out, int n, int Hs, int Ws) {
+  Gemm g;
+  IgemmArgs& a = g.a;
   memset(&a, 0, sizeof(a));
-  a.mask_bits = mask ? mask_bits : nullptr;
-  if (c1w && a.mask_bits) { a.c1w_img = c1w->img; a.c1w_part = c1w->part; a.c1w_part_floats = c1w->part_floats; a.c1w_scale = c1w->scale; a.c1w_skip_out = c1w->skip_out; }
-  if (stats && sp && sp->use) { a.stat_acc = sp->acc; a.stat_pg = sp->pg; a.stat_reps = sp->reps; a.fold = fold; }
-  if (bf && bf->planned) {
-    a.bwd_x = bf->x; a.bwd_ldx = bf->ldx; a.bwd_scale = bf->scale; a.bwd_shift = bf->shift; a.bwd_mean = bf->mean; a.bwd_inv = bf->inv;
-    a.bwd_stride = bf->stride; a.bwd_slope = bf->slope; a.bwd_acc = bf->acc; a.bwd_reps = bf->reps_gemm; a.bwd_pg = bf->pg;
-    a.bwd_c0 = bf->c0; a.bwd_c = bf->c;
-  }
-  a.relu_cend = relu_cend;
-  a.mask = mask; a.ldmask = ldmask; a.coffmask = 0; a.mask_slope = mask_slope;
-  a.add = add; a.ldadd = ldadd; a.coffadd = 0;
-  a.in = in; a.w = w; a.out = out; a.bias = bias;
-  a.partials = stats ? (float*)net->shared(net->oPart) : nullptr;
+  a.in = in.p; a.cin = in.c; a.ldin = in.ld; a.coffin = in.coff;
+  a.w = w;
+  a.out = (void*)out.p; a.cout = out.c; a.ldout = out.ld; a.coffout = out.coff;
+  a.n = n; a.Hs = Hs; a.Ws = Ws;
   a.ws = net->split_bytes > 0 ? (float*)net->shared(net->oSplit) : nullptr;
   a.ws_bytes = net->split_bytes;
   a.tickets = net->oTickets >= 0 ? (unsigned*)net->shared(net->oTickets) : nullptr;
-  a.n = n; a.Hs = Hs; a.Ws = Ws;
-  a.cin = cin; a.ldin = ldin; a.coffin = coffin;
-  a.cout = cout; a.ldout = ldout; a.coffout = coffout;
-  a.relu_in = relu_in; a.act_out = act_out;
+  return g;
+}
+// column statistics of the result for the BatchNorm that follows: partial rows, or with a plan in use the exact accumulators and
+// then, if offered, the normalisation pass folded into the launch (IgemmFold; the kernel decides: IgemmArgs::fold_applied)
+void with_stats(const gi_net* net, Gemm& g, StatPlan& sp, const IgemmFold* fold = nullptr) {
+  g.sp = &sp;
+  g.a.partials = (float*)net->shared(net->oPart);
+  if (sp.use) { g.a.stat_acc = sp.acc; g.a.stat_pg = sp.pg; g.a.stat_reps = sp.reps; g.a.fold = fold; }
+}
+// the BatchNorm-backward reduction of the layer the result is the output gradient of (bwd_fuse_plan)
+void with_bn_bwd(Gemm& g, BwdFuse& bf) {
+  g.bf = &bf;
+  if (!bf.planned) return;
+  IgemmArgs& a = g.a;
+  a.bwd_x = bf.x; a.bwd_ldx = bf.ldx; a.bwd_scale = bf.scale; a.bwd_shift = bf.shift; a.bwd_mean = bf.mean; a.bwd_inv = bf.inv;
+  a.bwd_stride = bf.stride; a.bwd_slope = bf.slope; a.bwd_acc = bf.acc; a.bwd_reps = bf.reps_gemm; a.bwd_pg = bf.pg;
+  a.bwd_c0 = bf.c0; a.bwd_c = bf.c;
+}
+// The result is the gradient at the output of the net's first layer (slot s; no norm, activation y1): its LeakyReLU backward rides
+// in the epilogue (IgemmArgs::mask; the generator names a second gradient, IgemmArgs::add, itself), reading the sign words the
+// forward wrote instead of y1 where it did (mask_bits). With the sign words the first layer's weight gradient can be formed
+// from the tiles while they are in LDS (c1w_*); without an input gradient to compute the result is then never stored.
+void with_first_layer_bwd(gi_net* net, int s, Gemm& g, Slice y1, bool need_wgrad, bool need_dx, C1WFuse& c1w) {
+  IgemmArgs& a = g.a;
+  a.mask = y1.p; a.ldmask = y1.ld; a.mask_slope = 0.2f;
+  if (net->slot_bits1[s] && gi_opt(GI_OPT_MASK_BITS)) a.mask_bits = (const unsigned long long*)net->slot(s, net->oBits1);
+  if (!a.mask_bits || !need_wgrad || net->oC1w < 0 || !gi_opt(GI_OPT_C1W_FUSE)) return;
+  c1w.img = (const float*)net->slot(s, net->oX); c1w.part = (float*)net->shared(net->oC1w); c1w.part_floats = net->c1w_floats - 64 * 1024;
+  c1w.scale = 1.f / net->loss_scale; c1w.skip_out = need_dx ? 0 : 1;
+  a.c1w_img = c1w.img; a.c1w_part = c1w.part; a.c1w_part_floats = c1w.part_floats; a.c1w_scale = c1w.scale; a.c1w_skip_out = c1w.skip_out;
+  g.c1w = &c1w;
+}
+// phase: op_igemm's mode (0: the stride-2 gather, 1: sub-pixel phases)
+int gemm_run(gi_net* net, int phase, Gemm& g) {
+  IgemmArgs& a = g.a;
   GI_TRY(op_igemm(net->ctx->stream, net->dtype, phase, a));
-  if (mask_applied) *mask_applied = a.mask_applied;
-  if (c1w) { c1w->applied = a.c1w_applied; c1w->blocks = a.c1w_blocks; }
-  if (fold_applied) *fold_applied = a.fold_applied;
-  if (bf && bf->planned) bf->applied = a.bwd_applied != 0;
-  if (sp && sp->use && !a.stat_used) sp->use = false;
-  if (ntiles) *ntiles = a.ntiles_out;
-  if (stats) GI_REQUIRE((int64_t)a.ntiles_out * 2 * cout <= net->part_floats, "internal: partials buffer too small");
+  if (g.c1w) { g.c1w->applied = a.c1w_applied; g.c1w->blocks = a.c1w_blocks; }
+  if (g.bf && g.bf->planned) g.bf->applied = a.bwd_applied != 0;
+  if (g.sp && g.sp->use && !a.stat_used) g.sp->use = false;
+  if (a.partials) GI_REQUIRE((int64_t)a.ntiles_out * 2 * a.cout <= net->part_floats, "internal: partials buffer too small");
   return GI_OK;
 }
+int gemm_run(gi_net* net, int phase, Gemm&& g) { return gemm_run(net, phase, g); }
 
-int wgrad(gi_net* net, const void* S, int ca, int ldS, int coffS, int relu_S, const void* L, int cb, int ldL, int coffL,
-          int n, int Hs, int Ws, float* dW) {
+WgradArgs wgrad_args(const gi_net* net, Slice S, Slice L, int n, int Hs, int Ws, float* dW) {
   WgradArgs a;
-  a.S = S; a.L = L; a.dW = dW; a.n = n; a.Hs = Hs; a.Ws = Ws;
-  a.ca = ca; a.ldS = ldS; a.coffS = coffS; a.cb = cb; a.ldL = ldL; a.coffL = coffL;
-  a.relu_S = relu_S; a.scale = 1.f / net->loss_scale;
+  a.S = S.p; a.L = L.p; a.dW = dW; a.n = n; a.Hs = Hs; a.Ws = Ws;
+  a.ca = S.c; a.ldS = S.ld; a.coffS = S.coff; a.cb = L.c; a.ldL = L.ld; a.coffL = L.coff;
+  a.relu_S = 0; a.scale = 1.f / net->loss_scale;
   a.scratch = net->wg_bytes > 0 ? (float*)net->shared(net->oWg) : nullptr;
   a.scratch_bytes = net->wg_bytes;
+  return a;
+}
+int wgrad_run(gi_net* net, const WgradArgs& a) {
   if (!net->side) return op_wgrad(net->ctx->stream, net->dtype, a);
   // second stream: starts when everything the chain has issued so far (dz of this level) is done; the event recorded behind it
   // guards the dz buffer of this level (side_dz)
@@ -935,9 +1016,22 @@ void* side_dz(gi_net* net) {
   return net->shared(net->oDr[net->dz_i]);
 }
 
-int act_bn_bwd(gi_net* net, int slot, const void* g1, int ldg1, int coffg1, const void* g2, int ldg2, int coffg2,
-               const void* y, int ldy, int coffy, const void* x, void* dx, int64_t pixels, int c, int act, float drop_scale,
-               const BN* bn, int need_wgrad, const BwdFuse* pre = nullptr) {
+// Backward through [dropout] -> activation -> [norm] of a layer with the saved activation y: act_bwd_args() fills what every call
+// needs, the call site names its gradient sources (set_g1 / set_g2, the latter masked by [y > 0]), the raw tensor x and drop_scale;
+// act_bn_bwd() adds what the net owns and launches into dx (dense), per BatchNorm population where they cannot share the launches.
+ActBnBwdArgs act_bwd_args(Slice y, int64_t pixels, int act) {
+  ActBnBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.y = y.p; a.ldy = y.ld; a.coffy = y.coff; a.c = y.c;
+  a.pixels = pixels; a.act = act; a.drop_scale = 1.f;
+  return a;
+}
+void set_g1(ActBnBwdArgs& a, Slice g) { a.g1 = g.p; a.ldg1 = g.ld; a.coffg1 = g.coff; }
+void set_g2(ActBnBwdArgs& a, Slice g) { a.g2 = g.p; a.ldg2 = g.ld; a.coffg2 = g.coff; }
+// bn: the layer's BatchNorm (none: activation backward only); pre: a reduction the producing GEMM was asked for (bwd_fuse_plan)
+int act_bn_bwd(gi_net* net, int slot, const ActBnBwdArgs& in, void* dx, const BN* bn = nullptr, int need_wgrad = 0, const BwdFuse* pre = nullptr) {
+  const int64_t pixels = in.pixels;
+  const int c = in.c;
   int g = (net->kind == 1 && bn) ? net->bn_groups : 1;   // BatchNorm groups: reductions per group
   int64_t pg = pixels / g;
   const int64_t T = (int64_t)net->tsz();
@@ -946,21 +1040,21 @@ int act_bn_bwd(gi_net* net, int slot, const void* g1, int ldg1, int coffg1, cons
                       (2 * (pg / op_bwd_rows_per_block(pg))) * 2 * c <= net->part_floats;
   if (merged) { g = 1; pg = pixels; }
   for (int j = 0; j < g; ++j) {
-    ActBnBwdArgs a;
-    memset(&a, 0, sizeof(a));
+    ActBnBwdArgs a = in;
     a.groups = merged ? 2 : 1; a.stat_stride = 4 * c;
     const int64_t o = (int64_t)j * pg;
-    a.g1 = g1 ? (const char*)g1 + o * ldg1 * T : nullptr; a.ldg1 = ldg1; a.coffg1 = coffg1;
-    a.g2 = g2 ? (const char*)g2 + o * ldg2 * T : nullptr; a.ldg2 = ldg2; a.coffg2 = coffg2;
-    a.y = (const char*)y + o * ldy * T; a.ldy = ldy; a.coffy = coffy;
-    a.x = x ? (const char*)x + o * c * T : nullptr; a.dx = (char*)dx + o * c * T;
-    a.pixels = pg; a.c = c; a.act = act; a.drop_scale = drop_scale;
+    if (a.g1) a.g1 = (const char*)in.g1 + o * a.ldg1 * T;
+    if (a.g2) a.g2 = (const char*)in.g2 + o * a.ldg2 * T;
+    a.y = (const char*)in.y + o * a.ldy * T;
+    if (a.x) a.x = (const char*)in.x + o * c * T;
+    a.dx = (char*)dx + o * c * T;
+    a.pixels = pg;
     a.has_bn = bn ? 1 : 0;
     a.eval_bn = net->bwd_eval;
     if (bn) {
       BNPtrs p = bn_ptrs(net, slot, *bn, j);
       a.gamma = net->params + bn->gamma_off; a.save_mean = p.mean; a.save_invstd = p.inv;
-      if (drop_scale == 1.f && x) { a.fwd_scale = p.scale; a.fwd_shift = p.shift; }   // dropout zeros live only in y
+      if (a.drop_scale == 1.f && a.x) { a.fwd_scale = p.scale; a.fwd_shift = p.shift; }   // dropout zeros live only in y
       a.dgamma = need_wgrad ? net->grads + bn->gamma_off : nullptr;
       a.dbeta = need_wgrad ? net->grads + bn->beta_off : nullptr;
     }
@@ -1079,66 +1173,82 @@ int unet_sync_inference(gi_net* net) {
   return GI_OK;
 }
 
-int unet_forward_inference(gi_net* net, int s, const float* x, float* y, int n) {
-  hipStream_t st = net->ctx->stream;
-  const int nd = net->nd, dt = net->dtype;
-  if (net->inf_gen != net->affine_gen) GI_TRY(unet_sync_inference(net));
-  net->slot_n[s] = n;
-  net->slot_train[s] = 0;
-  net->slot_inference[s] = 1;
-  net->slot_fused_u2[s] = 0;
-  auto C = [&](int k) { return (void*)net->slot(s, net->oC[k]); };
-  auto shift = [&](const BN& b) { return (const float*)net->shared(b.inf_off) + b.c; };
-  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, C(1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
-                      GI_ACT_LRELU, 1.f));
-  for (int k = 2; k <= nd; ++k) {
-    if (k < nd)
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, net->shared(net->conv[k].inf_off), C(k), net->ch[k],
-                   2 * net->ch[k], 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_LRELU, false, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr, 0,
-                   shift(net->dnorm[k])));
-    else
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, packed_ptr(net, net->conv[k]), net->slot(s, net->oE),
-                   net->ch[k], net->ch[k], 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_RELU, false, nullptr));
-  }
-  for (int k = nd; k >= 2; --k) {
-    const void* in = (k == nd) ? (const void*)net->slot(s, net->oE) : C(k);
-    const int cin = net->up[k].ca, co = net->ch[k - 1];
-    GI_TRY(igemm(net, 1, in, cin, cin, 0, net->shared(net->up[k].inf_off), C(k - 1), co, 2 * co, co, n, net->Hk[k], net->Wk[k], k < nd ? 1 : 0,
-                 GI_ACT_RELU, false, nullptr, k < nd ? net->ch[k] : 0, nullptr, 0, 0.f, nullptr, nullptr, 0, shift(net->unorm[k])));
-  }
-  float* osave = (float*)net->slot(s, net->oOut);
-  if (net->out_c == 1) {
-    GI_TRY(op_c1_scatter(st, dt, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, n, net->Hk[1],
-                         net->Wk[1], 2 * net->ch[1], 2 * net->ch[1], 0, 1, 1, 1.f, net->shared(net->oCol), y));
-    return GI_OK;
-  }
-  const int c1 = 2 * net->ch[1], H = net->H, W = net->W;
-  if (op_c1_head4_ok(dt, c1, net->out_c, net->Wk[1], c1, 0))   // the face-parsing network's head: 64-row col GEMM + overlap-add
-    return op_c1_head4_forward(st, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, y, n, net->Hk[1], net->Wk[1], c1,
-                               0, 1, net->shared(net->oCol));
-  void* U1 = net->shared(net->oU1);
-  GI_TRY(igemm(net, 1, C(1), c1, c1, 0, net->shared(net->oUp1Phase), U1, 64, 64, 0, n, net->Hk[1], net->Wk[1], 1, GI_ACT_NONE, false, nullptr,
-               net->ch[1]));
-  const int64_t total = (int64_t)n * net->out_c * H * W;
-  if (dt == GI_F16)
-    hipLaunchKernelGGL(head_tanh_kernel<half_t>, dim3(grid1d(total)), dim3(256), 0, st, (const half_t*)U1, net->params + net->up[1].bias_off, y, n,
-                       net->out_c, H * W);
-  else
-    hipLaunchKernelGGL(head_tanh_kernel<float>, dim3(grid1d(total)), dim3(256), 0, st, (const float*)U1, net->params + net->up[1].bias_off, y, n,
-                       net->out_c, H * W);
+int launch_head_tanh(gi_net* net, const void* u, float* y, int n) {
+  const int hw = net->H * net->W;
+  const float* bias = net->params + net->up[1].bias_off;
+  const dim3 grid(grid1d((int64_t)n * net->out_c * hw));
+  if (net->dtype == GI_F16) hipLaunchKernelGGL(head_tanh_kernel<half_t>, grid, dim3(256), 0, net->ctx->stream, (const half_t*)u, bias, y, n, net->out_c, hw);
+  else hipLaunchKernelGGL(head_tanh_kernel<float>, grid, dim3(256), 0, net->ctx->stream, (const float*)u, bias, y, n, net->out_c, hw);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int launch_pad_dy(gi_net* net, const float* g, void* out, int n) {
+  const int hw = net->H * net->W;
+  const dim3 grid(grid1d((int64_t)n * hw * 64));
+  if (net->dtype == GI_F16) hipLaunchKernelGGL(pad_dy_kernel<half_t>, grid, dim3(256), 0, net->ctx->stream, g, (half_t*)out, n, net->out_c, hw);
+  else hipLaunchKernelGGL(pad_dy_kernel<float>, grid, dim3(256), 0, net->ctx->stream, g, (float*)out, n, net->out_c, hw);
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
 
-// generator with InstanceNorm2d / without norm layers: the normalisation step after a convolution (raw -> dst with
-// activation and dropout). InstanceNorm keeps (mean, inv) per image and channel in the slot for the backward.
-int plain_norm_forward(gi_net* net, int slot, const BN& b, const void* raw, int n, int hw, void* dst, int ldy, int coffy, int act,
-                       const uint8_t* drop, float drop_scale) {
+// The last decoder level of the BatchNorm generator feeds only the single-channel head: its BatchNorm + ReLU is applied by the
+// head's kernels while they read the raw tensor, so the upper half of the level-1 concat buffer is never written
+C1Affine u2_affine(const gi_net* net, int s) {
+  BNPtrs p = bn_ptrs(net, s, net->unorm[2]);
+  C1Affine aff;
+  aff.x2 = net->slot(s, net->oU[2]); aff.ld2 = net->ch[1]; aff.scale = p.scale; aff.shift = p.shift;
+  return aff;
+}
+
+// u1: ConvTranspose2d(2 ngf -> out_c) + bias + Tanh of the level-1 concat buffer into y (n, out_c, H, W) fp32. save: also into
+// the slot, for the backward (an inference forward does not). aff: u2_affine.
+int head_forward(gi_net* net, int s, float* y, int n, bool save, const C1Affine* aff = nullptr) {
   hipStream_t st = net->ctx->stream;
-  if (net->norm_kind == 1)
-    return op_in_forward(st, net->dtype, raw, dst, n, hw, b.c, ldy, coffy, act, drop, drop_scale, 1e-5f,
-                         (float*)net->slot(slot, net->oInStats) + b.in_off);
-  return op_bn_apply(st, net->dtype, raw, dst, (int64_t)n * hw, b.c, ldy, coffy, nullptr, nullptr, act, drop, drop_scale);
+  const int dt = net->dtype, c1 = 2 * net->ch[1], Hs = net->Hk[1], Ws = net->Wk[1];
+  const void* X = concat_buf(net, s, 1);
+  const float* w = net->params + net->up[1].w_off;
+  const float* bias = net->params + net->up[1].bias_off;
+  float* osave = (float*)net->slot(s, net->oOut);
+  if (net->out_c == 1)   // y written beside the saved output
+    return op_c1_scatter(st, dt, X, w, bias, osave, n, Hs, Ws, c1, c1, 0, 1, 1, 1.f, net->shared(net->oCol), y, aff);
+  if (op_c1_head4_ok(dt, c1, net->out_c, Ws, c1, 0))   // the face-parsing network's head: 64-row col GEMM + overlap-add
+    return op_c1_head4_forward(st, X, w, bias, osave, y, n, Hs, Ws, c1, 0, 1, net->shared(net->oCol));
+  // out_c channels: the same sub-pixel GEMM as the other up-convolutions on weights zero-padded to 64 output channels,
+  // then bias + tanh of the first out_c channels
+  void* U1 = net->shared(net->oU1);
+  Gemm g = gemm_args(net, sl(X, c1), net->shared(net->oUp1Phase), sl(U1, 64), n, Hs, Ws);
+  g.a.relu_in = 1; g.a.relu_cend = net->ch[1];
+  GI_TRY(gemm_run(net, 1, g));
+  GI_TRY(launch_head_tanh(net, U1, save ? osave : y, n));
+  if (save) GI_HIP(hipMemcpyAsync(y, osave, (size_t)n * net->out_c * net->H * net->W * 4, hipMemcpyDeviceToDevice, st));
+  return GI_OK;
+}
+
+// backward of head_forward: tanh' and loss scaling of dy into G0, u1's bias and weight gradients, the gradient of the level-1
+// concat buffer into ogC[1]
+int head_backward(gi_net* net, int s, const float* dy, int need_wgrad, const C1Affine* aff = nullptr) {
+  hipStream_t st = net->ctx->stream;
+  const int dt = net->dtype, n = net->slot_n[s], c1 = 2 * net->ch[1], Hs = net->Hk[1], Ws = net->Wk[1];
+  const int64_t npx = (int64_t)n * net->H * net->W;
+  const float iLS = 1.f / net->loss_scale;
+  float* G0 = (float*)net->shared(net->oG0);
+  const float* w = net->params + net->up[1].w_off;
+  void* g1 = net->shared(net->ogC[1]);
+  GI_TRY(op_tanh_bwd(st, dy, (const float*)net->slot(s, net->oOut), G0, npx * net->out_c, net->loss_scale));
+  if (need_wgrad) {
+    // (the u1 bias gradient: a sum over every output pixel, fixed order)
+    hipLaunchKernelGGL(sum_part_kernel, dim3(256), dim3(256), 0, st, G0, npx, (double*)net->shared(net->oPart));
+    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)net->shared(net->oPart), 256, net->grads + net->up[1].bias_off, iLS);
+    GI_LAUNCH_CHECK();
+    GI_TRY(op_c1_wgrad(st, dt, concat_buf(net, s, 1), G0, net->grads + net->up[1].w_off, n, Hs, Ws, c1, c1, 0, 1, iLS, 1.f, aff,
+                       (float*)net->shared(net->oPart), net->part_floats));
+  }
+  if (net->out_c == 1) return op_c1_gather(st, dt, G0, w, g1, n, Hs, Ws, c1, c1, 0, GI_ACT_NONE, 1.f);
+  if (op_c1_head4_ok(dt, c1, net->out_c, Ws, c1, 0)) return op_c1_head4_dgrad(st, G0, w, g1, n, Hs, Ws, c1, 0);
+  void* U1 = net->shared(net->oU1);
+  GI_TRY(launch_pad_dy(net, G0, U1, n));
+  const void* wp = net->oUp1Packed >= 0 ? (const void*)net->shared(net->oUp1Packed) : (const void*)net->shared(net->oUp1Pad);
+  return gemm_run(net, 0, gemm_args(net, sl(U1, 64), wp, sl(g1, c1), n, Hs, Ws));
 }
 
 const float* conv_bias(const gi_net* net, const Conv& c) { return c.bias_off >= 0 ? net->params + c.bias_off : nullptr; }
@@ -1151,8 +1261,81 @@ int bias_grad(gi_net* net, const Conv& c, const void* dz, int64_t pixels, int ch
                       (float*)net->shared(net->oPart));
 }
 
+// The end of a backward at the net's first layer cv (single-channel input, (n, Hs, Ws, c) output, no norm). a1: its activation
+// backward; it is skipped when the second layer's input-gradient GEMM already applied it to a1.g1
+// (lrelu1_done, with_first_layer_bwd). Then the layer's weight (and bias) gradient - from the partial sums of that GEMM where it
+// formed them (c1w) - and, if asked for, the input gradient dx.
+int first_layer_tail(gi_net* net, int s, const Conv& cv, int n, int Hs, int Ws, const ActBnBwdArgs& a1, int need_wgrad, float* dx,
+                     int lrelu1_done = 0, const C1WFuse* c1w = nullptr) {
+  hipStream_t st = net->ctx->stream;
+  const int dt = net->dtype, c = a1.c;
+  const float iLS = 1.f / net->loss_scale;
+  float* dW = net->grads + cv.w_off;
+  void* D = side_dz(net);
+  const void* D1 = lrelu1_done ? a1.g1 : D;
+  if (!lrelu1_done) GI_TRY(act_bn_bwd(net, s, a1, D));
+  if (need_wgrad) GI_TRY(bias_grad(net, cv, D1, a1.pixels, c));
+  if (need_wgrad && c1w && c1w->applied)
+    GI_TRY(op_c1_wgrad_reduce(st, c1w->part, dW, c * 16, c1w->blocks, c1w->part + (int64_t)c1w->blocks * 1024,
+                              net->c1w_floats - (int64_t)c1w->blocks * 1024));
+  else if (need_wgrad)
+    GI_TRY(op_c1_wgrad(st, dt, D1, (const float*)net->slot(s, net->oX), dW, n, Hs, Ws, c, c, 0, 0, iLS, 1.f, nullptr,
+                       (float*)net->shared(net->oPart), net->part_floats));
+  if (dx) GI_TRY(op_c1_scatter(st, dt, D1, net->params + cv.w_off, nullptr, dx, n, Hs, Ws, c, c, 0, 0, 0, iLS, net->shared(net->oCol)));
+  return GI_OK;
+}
+
+int unet_forward_inference(gi_net* net, int s, const float* x, float* y, int n) {
+  hipStream_t st = net->ctx->stream;
+  const int nd = net->nd, dt = net->dtype;
+  if (net->inf_gen != net->affine_gen) GI_TRY(unet_sync_inference(net));
+  net->slot_n[s] = n;
+  net->slot_train[s] = 0;
+  net->slot_inference[s] = 1;
+  net->slot_fused_u2[s] = 0;
+  auto shift = [&](const BN& b) { return (const float*)net->shared(b.inf_off) + b.c; };
+  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, concat_buf(net, s, 1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
+                      GI_ACT_LRELU, 1.f));
+  for (int k = 2; k < nd; ++k) {
+    Gemm g = gemm_args(net, skip_half(net, s, k - 1), net->shared(net->conv[k].inf_off), skip_half(net, s, k), n, net->Hk[k], net->Wk[k]);
+    g.a.act_out = GI_ACT_LRELU; g.a.bias = shift(net->dnorm[k]);
+    GI_TRY(gemm_run(net, 0, g));
+  }
+  {
+    Gemm g = gemm_args(net, skip_half(net, s, nd - 1), packed_ptr(net, net->conv[nd]), up_input(net, s, nd), n, net->Hk[nd], net->Wk[nd]);
+    g.a.act_out = GI_ACT_RELU;
+    GI_TRY(gemm_run(net, 0, g));
+  }
+  for (int k = nd; k >= 2; --k) {
+    Gemm g = gemm_args(net, up_input(net, s, k), net->shared(net->up[k].inf_off), up_half(net, s, k - 1), n, net->Hk[k], net->Wk[k]);
+    if (k < nd) { g.a.relu_in = 1; g.a.relu_cend = net->ch[k]; }
+    g.a.act_out = GI_ACT_RELU; g.a.bias = shift(net->unorm[k]);
+    GI_TRY(gemm_run(net, 1, g));
+  }
+  return head_forward(net, s, y, n, false);
+}
+
+// generator with InstanceNorm2d / without norm layers: the normalisation step after a convolution (raw -> dst with
+// activation and dropout). InstanceNorm keeps (mean, inv) per image and channel in the slot for the backward.
+int plain_norm_forward(gi_net* net, int slot, const BN& b, const void* raw, int n, int hw, Slice dst, int act, const Dropout& drop = Dropout()) {
+  hipStream_t st = net->ctx->stream;
+  if (net->norm_kind == 1)
+    return op_in_forward(st, net->dtype, raw, (void*)dst.p, n, hw, b.c, dst.ld, dst.coff, act, drop.mask, drop.scale, 1e-5f,
+                         (float*)net->slot(slot, net->oInStats) + b.in_off);
+  return op_bn_apply(st, net->dtype, raw, (void*)dst.p, (int64_t)n * hw, b.c, dst.ld, dst.coff, nullptr, nullptr, act, drop.mask, drop.scale);
+}
+
 int unet_forward_plain(gi_net* net, int s, const float* x, float* y, int n);
 int unet_backward_plain(gi_net* net, int s, const float* dy, float* dx, int need_wgrad, int phase);
+
+// the normalisation pass of a small layer offered to the GEMM that produces it (IgemmFold; igemm7 decides)
+IgemmFold fold_offer(const gi_net* net, int s, const BN& b, const StatPlan& sp, int64_t pixels, Slice dst, int act, const Dropout& drop = Dropout()) {
+  IgemmFold fold;
+  fold.bn = bn_acc_args(net, s, b, sp, pixels, 1);
+  fold.dst = (void*)dst.p; fold.lddst = dst.ld; fold.coffdst = dst.coff; fold.act = act;
+  fold.drop_mask = drop.mask; fold.drop_scale = drop.scale; fold.drop_seed = drop.seed; fold.drop_p = drop.p;
+  return fold;
+}
 
 int unet_forward(gi_net* net, int s, const float* x, float* y, int n) {
   hipStream_t st = net->ctx->stream;
@@ -1161,131 +1344,69 @@ int unet_forward(gi_net* net, int s, const float* x, float* y, int n) {
   if (!train && net->inference && nd >= 3) return unet_forward_inference(net, s, x, y, n);
   net->slot_inference[s] = 0;
   if (train) ++net->affine_gen;   // running statistics change below
-  const int H = net->H, W = net->W;
   net->slot_n[s] = n;
   net->slot_train[s] = train;
   const bool fuse_u2 = nd >= 3 && net->out_c == 1 && net->fuse_head && op_c1_affine_ok(dt, 2 * net->ch[1], net->Wk[1], 2 * net->ch[1], 0);
   net->slot_fused_u2[s] = fuse_u2 ? 1 : 0;
-  auto C = [&](int k) { return (void*)net->slot(s, net->oC[k]); };
   // d1: Conv2d(1->ngf) then the next block's in-place LeakyReLU (networks.py:287): the skip IS lrelu(x)
-  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, C(1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
+  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, concat_buf(net, s, 1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
                       GI_ACT_LRELU, 1.f, nullptr, gi_opt(GI_OPT_MASK_BITS) ? (unsigned long long*)net->slot(s, net->oBits1) : nullptr, &net->slot_bits1[s]));
-  // the copy of the input that d1's weight gradient reads (8.4 MB at the headline shape) rides in d2's normalisation pass
-  // (bn_forward's side copy); where that pass does not exist, a device copy
   bool x_saved = false;
-  for (int k = 2; k <= nd; ++k) {
+  for (int k = 2; k < nd; ++k) {
     const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
-    int nt = 0;
-    if (k < nd) {
-      void* R = net->slot(s, net->oR[k]);
-      StatPlan sp = stat_plan(net, net->dnorm[k], pix, (pix + 127) / 128, train);
-      // small layers: the GEMM's last finisher per channel column normalises the column itself (IgemmFold; igemm7 decides)
-      IgemmFold fold;
-      int folded = 0;
-      if (sp.use && dt == GI_F16) {
-        fold.bn = bn_acc_args(net, s, net->dnorm[k], sp, pix, 1);
-        fold.dst = C(k); fold.lddst = 2 * net->ch[k]; fold.coffdst = 0; fold.act = GI_ACT_LRELU;
-        fold.drop_mask = nullptr; fold.drop_scale = 1.f; fold.drop_seed = 0; fold.drop_p = 0.f;
-      }
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, packed_ptr(net, net->conv[k]), R, net->ch[k],
-                   net->ch[k], 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_NONE, true, &nt, 0, nullptr, 0, 0.f, nullptr, nullptr, 0, nullptr, &sp, nullptr,
-                   (sp.use && dt == GI_F16) ? &fold : nullptr, &folded));
-      if (folded) { bn_acc_commit(net, s, net->dnorm[k], sp); continue; }
-      const bool side = !x_saved && k == 2 && sp.use && ((int64_t)n * H * W * 4) % 16 == 0;
-      GI_TRY(bn_forward(net, s, net->dnorm[k], R, pix, nt, C(k), 2 * net->ch[k], 0, GI_ACT_LRELU, nullptr, 1.f, train, true, &sp, 0.f, 0,
-                        side ? x : nullptr, side ? net->slot(s, net->oX) : nullptr, side ? (int64_t)n * H * W * 4 : 0));
-      if (side) x_saved = true;
-    } else {  // innermost: no down-norm; uprelu follows directly (networks.py:299-305)
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, packed_ptr(net, net->conv[k]), net->slot(s, net->oE),
-                   net->ch[k], net->ch[k], 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_RELU, false, nullptr));
-    }
+    void* R = net->slot(s, net->oR[k]);
+    StatPlan sp = stat_plan(net, net->dnorm[k], pix, (pix + 127) / 128, train);
+    const bool offer = sp.use && dt == GI_F16;   // small layers: the GEMM's last finisher per channel column normalises the column itself
+    IgemmFold fold;
+    if (offer) fold = fold_offer(net, s, net->dnorm[k], sp, pix, skip_half(net, s, k), GI_ACT_LRELU);
+    Gemm g = gemm_args(net, skip_half(net, s, k - 1), packed_ptr(net, net->conv[k]), sl(R, net->ch[k]), n, net->Hk[k], net->Wk[k]);
+    with_stats(net, g, sp, offer ? &fold : nullptr);
+    GI_TRY(gemm_run(net, 0, g));
+    if (g.a.fold_applied) { bn_acc_commit(net, s, net->dnorm[k], sp); continue; }
+    BnOpts o;
+    if (k == 2) o.side = input_side_copy(net, s, x, n, sp);
+    GI_TRY(bn_forward(net, s, net->dnorm[k], R, pix, g.a.ntiles_out, skip_half(net, s, k), GI_ACT_LRELU, train, sp, o));
+    if (o.side.bytes > 0) x_saved = true;
+  }
+  {  // innermost: no down-norm; uprelu follows directly (networks.py:299-305)
+    Gemm g = gemm_args(net, skip_half(net, s, nd - 1), packed_ptr(net, net->conv[nd]), up_input(net, s, nd), n, net->Hk[nd], net->Wk[nd]);
+    g.a.act_out = GI_ACT_RELU;
+    GI_TRY(gemm_run(net, 0, g));
   }
   BnAccArgs u2_acc;
   bool u2_deferred = false;
-  if (!x_saved) GI_HIP(hipMemcpyAsync(net->slot(s, net->oX), x, (size_t)n * H * W * 4, hipMemcpyDeviceToDevice, st));
+  if (!x_saved) GI_TRY(input_copy(net, s, x, n));
   for (int k = nd; k >= 2; --k) {
-    const void* in = (k == nd) ? (const void*)net->slot(s, net->oE) : C(k);
-    const int cin = net->up[k].ca;
-    const int64_t opix = (int64_t)n * net->Hk[k - 1] * net->Wk[k - 1];
-    const int co = net->ch[k - 1];
+    const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k], opix = 4 * pix;
     void* U = net->slot(s, net->oU[k]);
-    int nt = 0;
-    StatPlan sp = stat_plan(net, net->unorm[k], (int64_t)n * net->Hk[k] * net->Wk[k], ((int64_t)n * net->Hk[k] * net->Wk[k] + 127) / 128 * 4, train);
-    const uint8_t* drop = nullptr;
-    float drop_p = 0.f;
-    uint64_t drop_seed = 0;
-    if (train && net->dropout_p > 0.f && k >= 5 && k <= nd - 1) {
-      uint8_t* m = (uint8_t*)net->slot(s, net->oMask[k]);
-      if (net->ext_mask[s][k]) {
-        GI_TRY(op_mask_nchw_to_nhwc(st, net->ext_mask[s][k], m, n, co, net->Hk[k - 1] * net->Wk[k - 1], 1));
-      } else {
-        drop_seed = net->drop_seed + 0x1000003ull * (++net->drop_counter);
-      }
-      drop = m;
-    }
+    StatPlan sp = stat_plan(net, net->unorm[k], pix, (pix + 127) / 128 * 4, train);
+    Dropout drop;
+    GI_TRY(dropout_prepare(net, s, k, n, true, drop));
     const bool fused = (k == 2) && fuse_u2;
-    IgemmFold fold;
-    int folded = 0;
     const bool offer = sp.use && dt == GI_F16 && !fused;
-    if (offer) {
-      fold.bn = bn_acc_args(net, s, net->unorm[k], sp, opix, 1);
-      fold.dst = C(k - 1); fold.lddst = 2 * co; fold.coffdst = co; fold.act = GI_ACT_RELU;
-      fold.drop_mask = (uint8_t*)drop; fold.drop_scale = drop ? 1.f / (1.f - net->dropout_p) : 1.f;
-      fold.drop_seed = drop_seed; fold.drop_p = (drop && !net->ext_mask[s][k]) ? net->dropout_p : 0.f;
-    }
-    GI_TRY(igemm(net, 1, in, cin, cin, 0, phase_ptr(net, net->up[k]), U, co, co, 0, n, net->Hk[k], net->Wk[k], k < nd ? 1 : 0,
-                 GI_ACT_NONE, true, &nt, k < nd ? net->ch[k] : 0, nullptr, 0, 0.f, nullptr, nullptr, 0, nullptr, &sp, nullptr, offer ? &fold : nullptr,
-                 &folded));
-    if (folded) { bn_acc_commit(net, s, net->unorm[k], sp); continue; }
-    if (drop && !net->ext_mask[s][k]) {
-      if (sp.use) drop_p = net->dropout_p;      // drawn (same hash, same masks) inside the normalisation pass
-      else GI_TRY(op_fill_dropout(st, (uint8_t*)drop, opix * co, drop_seed, net->dropout_p));
-    }
+    IgemmFold fold;
+    if (offer) fold = fold_offer(net, s, net->unorm[k], sp, opix, up_half(net, s, k - 1), GI_ACT_RELU, drop);
+    Gemm g = gemm_args(net, up_input(net, s, k), phase_ptr(net, net->up[k]), sl(U, net->ch[k - 1]), n, net->Hk[k], net->Wk[k]);
+    if (k < nd) { g.a.relu_in = 1; g.a.relu_cend = net->ch[k]; }
+    with_stats(net, g, sp, offer ? &fold : nullptr);
+    GI_TRY(gemm_run(net, 1, g));
+    if (g.a.fold_applied) { bn_acc_commit(net, s, net->unorm[k], sp); continue; }
+    if (drop.p > 0.f && !sp.use) GI_TRY(dropout_draw(net, drop, opix * net->ch[k - 1]));   // (else drawn inside the normalisation pass)
     // the decoder half is only ever consumed through the parent's in-place ReLU (networks.py:289): store
     // relu(u) so that consumers need the ReLU on the skip half only; [u > 0] masks are unchanged
-    // the last decoder level feeds only the single-channel head: its BatchNorm + ReLU is applied by the head's
-    // kernels while they read the raw tensor (C1Affine), so the upper half of C(1) is never written
-    if (fused && sp.use && net->out_c == 1) {   // the head's first kernel derives scale / shift itself (C1Affine::bn): no finalize launch
+    if (fused && sp.use) {   // the head's first kernel derives u2's scale / shift itself (C1Affine::bn): no finalize launch
       u2_acc = bn_acc_args(net, s, net->unorm[k], sp, opix, 1);
       bn_acc_commit(net, s, net->unorm[k], sp);
       u2_deferred = true;
       continue;
     }
-    GI_TRY(bn_forward(net, s, net->unorm[k], U, opix, nt, C(k - 1), 2 * co, co, GI_ACT_RELU, drop,
-                      drop ? 1.f / (1.f - net->dropout_p) : 1.f, train, !fused, &sp, drop_p, drop_seed));
+    BnOpts o;
+    o.apply = !fused; o.drop = drop;
+    GI_TRY(bn_forward(net, s, net->unorm[k], U, opix, g.a.ntiles_out, up_half(net, s, k - 1), GI_ACT_RELU, train, sp, o));
   }
-  float* osave = (float*)net->slot(s, net->oOut);
-  if (net->out_c == 1) {
-    C1Affine aff;
-    if (fuse_u2) {
-      BNPtrs p = bn_ptrs(net, s, net->unorm[2]);
-      aff.x2 = net->slot(s, net->oU[2]); aff.ld2 = net->ch[1]; aff.scale = p.scale; aff.shift = p.shift;
-      if (u2_deferred) aff.bn = &u2_acc;
-    }
-    GI_TRY(op_c1_scatter(st, dt, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, n, net->Hk[1],
-                         net->Wk[1], 2 * net->ch[1], 2 * net->ch[1], 0, 1, 1, 1.f, net->shared(net->oCol), y, fuse_u2 ? &aff : nullptr));
-    return GI_OK;   // y written beside the saved output
-  } else {
-    // u1 with out_c channels: the same sub-pixel GEMM as the other up-convolutions on weights zero-padded to 64
-    // output channels, then bias + tanh of the first out_c channels into the (n,out_c,H,W) fp32 result
-    const int c1 = 2 * net->ch[1];
-    if (op_c1_head4_ok(dt, c1, net->out_c, net->Wk[1], c1, 0))   // the face-parsing network's head: 64-row col GEMM + overlap-add
-      return op_c1_head4_forward(st, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, y, n, net->Hk[1], net->Wk[1], c1,
-                                 0, 1, net->shared(net->oCol));
-    void* U1 = net->shared(net->oU1);
-    GI_TRY(igemm(net, 1, C(1), c1, c1, 0, net->shared(net->oUp1Phase), U1, 64, 64, 0, n, net->Hk[1], net->Wk[1], 1, GI_ACT_NONE, false,
-                 nullptr, net->ch[1]));
-    const int64_t total = (int64_t)n * net->out_c * H * W;
-    if (dt == GI_F16)
-      hipLaunchKernelGGL(head_tanh_kernel<half_t>, dim3(grid1d(total)), dim3(256), 0, st, (const half_t*)U1, net->params + net->up[1].bias_off,
-                         osave, n, net->out_c, H * W);
-    else
-      hipLaunchKernelGGL(head_tanh_kernel<float>, dim3(grid1d(total)), dim3(256), 0, st, (const float*)U1, net->params + net->up[1].bias_off,
-                         osave, n, net->out_c, H * W);
-    GI_LAUNCH_CHECK();
-  }
-  GI_HIP(hipMemcpyAsync(y, osave, (size_t)n * net->out_c * H * W * 4, hipMemcpyDeviceToDevice, st));
-  return GI_OK;
+  C1Affine aff = u2_affine(net, s);
+  if (u2_deferred) aff.bn = &u2_acc;
+  return head_forward(net, s, y, n, true, fuse_u2 ? &aff : nullptr);
 }
 
 // phase: 0 = whole backward; 1 = decoder half (u1 .. u_nd: their parameter gradients occupy the tail
@@ -1293,9 +1414,7 @@ int unet_forward(gi_net* net, int s, const float* x, float* y, int n) {
 // Splitting lets the host start the decoder gradients' all-reduce while the encoder half runs.
 int unet_backward(gi_net* net, int s, const float* dy, float* dx, int need_wgrad, int phase) {
   if (net->norm_kind != 0) return unet_backward_plain(net, s, dy, dx, need_wgrad, phase);
-  hipStream_t st = net->ctx->stream;
-  const int nd = net->nd, dt = net->dtype;
-  const int H = net->H, W = net->W, n = net->slot_n[s];
+  const int nd = net->nd, n = net->slot_n[s];
   // a forward in eval mode (running-statistics BatchNorm, no dropout) can be differentiated w.r.t. its input only:
   // the frozen segmentation network of the face-parsing loss (wgan_perceptual_style_faceparsing.py:212-213)
   GI_REQUIRE(n > 0 && (net->slot_train[s] || !need_wgrad), "unet_backward: slot %d holds no train-mode forward", s);
@@ -1303,80 +1422,46 @@ int unet_backward(gi_net* net, int s, const float* dy, float* dx, int need_wgrad
   GI_REQUIRE(net->out_c == 1 || !need_wgrad, "unet_backward: parameter gradients of a %d-channel generator are not built", net->out_c);
   const int evalbn = net->slot_train[s] ? 0 : 1;
   net->bwd_eval = evalbn;
-  const float LS = net->loss_scale, iLS = 1.f / LS;
-  auto C = [&](int k) { return (void*)net->slot(s, net->oC[k]); };
   auto gC = [&](int k) { return (void*)net->shared(net->ogC[k]); };
   auto gA = [&](int k) { return (void*)net->shared(net->ogA[k]); };
-  void* D = net->shared(net->oD);   // dz of the level in progress (side_dz: rotates when the weight gradients run on the second stream)
-  float* G0 = (float*)net->shared(net->oG0);
-  const int64_t npx = (int64_t)n * H * W;
+  auto dropped = [&](int k) { return !evalbn && net->dropout_p > 0.f && k >= 5 && k <= nd - 1; };   // decoder level k ran with dropout
+  void* D = nullptr;   // dz of the level in progress (side_dz: rotates when the weight gradients run on the second stream)
   if (phase == 0 || phase == 1) {
-  // tanh' and loss scaling
-  GI_TRY(op_tanh_bwd(st, dy, (const float*)net->slot(s, net->oOut), G0, npx * net->out_c, LS));
-  // u1: ConvTranspose2d(2ngf -> 1) + bias
-  const int c1 = 2 * net->ch[1];
-  if (need_wgrad) {
-    // (the u1 bias gradient: a sum over every output pixel, fixed order)
-    hipLaunchKernelGGL(sum_part_kernel, dim3(256), dim3(256), 0, st, G0, npx, (double*)net->shared(net->oPart));
-    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)net->shared(net->oPart), 256, net->grads + net->up[1].bias_off, iLS);
-    GI_LAUNCH_CHECK();
-    C1Affine aff;
-    const bool fused = net->slot_fused_u2[s] != 0;
-    if (fused) {   // the upper half of C(1) was never written (unet_forward): recompute it from the raw decoder output
-      BNPtrs p = bn_ptrs(net, s, net->unorm[2]);
-      aff.x2 = net->slot(s, net->oU[2]); aff.ld2 = net->ch[1]; aff.scale = p.scale; aff.shift = p.shift;
+    // the upper half of the level-1 concat buffer was never written where the forward fused u2 into the head: recomputed from the raw decoder output
+    C1Affine aff = u2_affine(net, s);
+    GI_TRY(head_backward(net, s, dy, need_wgrad, net->slot_fused_u2[s] ? &aff : nullptr));
+    GI_TRY(clear_pending_bwd(net, &net->unorm[2], nd - 1));
+    // decoder, outermost -> innermost: level k's concat gradient feeds up[k+1]
+    for (int k = 1; k <= nd - 1; ++k) {
+      const int kk = k + 1, ck = net->ch[k], ca = net->up[kk].ca;
+      const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
+      D = side_dz(net);
+      BwdFuse& pend = net->bwd_pending[net->unorm[kk].id];
+      ActBnBwdArgs b = act_bwd_args(up_half(net, s, k), pix, GI_ACT_NONE);
+      set_g2(b, sl(gC(k), ck, 2 * ck, ck));
+      b.x = net->slot(s, net->oU[kk]);
+      if (dropped(kk)) b.drop_scale = 1.f / (1.f - net->dropout_p);
+      GI_TRY(act_bn_bwd(net, s, b, D, &net->unorm[kk], need_wgrad, &pend));
+      pend = BwdFuse();
+      if (need_wgrad) {
+        WgradArgs wa = wgrad_args(net, up_input(net, s, kk), sl(D, ck), n, net->Hk[kk], net->Wk[kk], net->grads + net->up[kk].w_off);
+        wa.relu_S = kk < nd ? 1 : 0;
+        GI_TRY(wgrad_run(net, wa));
+      }
+      void* gout = (kk == nd) ? (void*)net->shared(net->ogE) : gC(kk);
+      Gemm g = gemm_args(net, sl(D, ck), packed_ptr(net, net->up[kk]), sl(gout, ca), n, net->Hk[kk], net->Wk[kk]);
+      // the upper half of this GEMM's columns is the gradient at the output of the NEXT decoder level's BatchNorm (its ReLU is the
+      // consumer's): that layer's backward reduction rides in the epilogue (IgemmArgs::bwd_c0; levels without dropout, kernels that take it)
+      const int kn = kk + 1;
+      if (kk <= nd - 1 && !dropped(kn)) {
+        const int64_t pixn = (int64_t)n * net->Hk[kk] * net->Wk[kk];
+        BwdFuse& bf = net->bwd_pending[net->unorm[kn].id];
+        bf = bwd_fuse_plan(net, s, net->unorm[kn], net->slot(s, net->oU[kn]), pixn, pixn / 256, 0.f);
+        bf.c0 = ca / 2; bf.c = ca / 2;
+        with_bn_bwd(g, bf);
+      }
+      GI_TRY(gemm_run(net, 0, g));
     }
-    GI_TRY(op_c1_wgrad(st, dt, C(1), G0, net->grads + net->up[1].w_off, n, net->Hk[1], net->Wk[1], c1, c1, 0, 1, iLS, 1.f, fused ? &aff : nullptr,
-                       (float*)net->shared(net->oPart), net->part_floats));
-  }
-  if (net->out_c == 1) {
-    GI_TRY(op_c1_gather(st, dt, G0, net->params + net->up[1].w_off, gC(1), n, net->Hk[1], net->Wk[1], c1, c1, 0, GI_ACT_NONE, 1.f));
-  } else if (op_c1_head4_ok(dt, c1, net->out_c, net->Wk[1], c1, 0)) {
-    GI_TRY(op_c1_head4_dgrad(st, G0, net->params + net->up[1].w_off, gC(1), n, net->Hk[1], net->Wk[1], c1, 0));
-  } else {
-    void* U1 = net->shared(net->oU1);
-    if (dt == GI_F16) hipLaunchKernelGGL(pad_dy_kernel<half_t>, dim3(grid1d(npx * 64)), dim3(256), 0, st, G0, (half_t*)U1, n, net->out_c, H * W);
-    else hipLaunchKernelGGL(pad_dy_kernel<float>, dim3(grid1d(npx * 64)), dim3(256), 0, st, G0, (float*)U1, n, net->out_c, H * W);
-    GI_LAUNCH_CHECK();
-    const void* wp = net->oUp1Packed >= 0 ? (const void*)net->shared(net->oUp1Packed) : (const void*)net->shared(net->oUp1Pad);
-    GI_TRY(igemm(net, 0, U1, 64, 64, 0, wp, gC(1), c1, c1, 0, n, net->Hk[1], net->Wk[1], 0, GI_ACT_NONE, false, nullptr));
-  }
-  // decoder, outermost -> innermost: level k's concat gradient feeds up[k+1]
-  // a reduction planned by an earlier, abandoned backward left sums in its accumulator block
-  for (int k = 2; k <= nd; ++k) {
-    if (net->unorm[k].c == 0 || net->unorm[k].id < 0) continue;
-    BwdFuse& pend = net->bwd_pending[net->unorm[k].id];
-    if (pend.planned) GI_HIP(hipMemsetAsync(pend.acc, 0, (size_t)net->unorm[k].acc_block() * 8, st));
-    pend = BwdFuse();
-  }
-  for (int k = 1; k <= nd - 1; ++k) {
-    const int kk = k + 1;
-    const int ck = net->ch[k];
-    const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
-    const float ds = (!evalbn && net->dropout_p > 0.f && kk >= 5 && kk <= nd - 1) ? 1.f / (1.f - net->dropout_p) : 1.f;
-    D = side_dz(net);
-    BwdFuse& pend = net->bwd_pending[net->unorm[kk].id];
-    GI_TRY(act_bn_bwd(net, s, nullptr, 0, 0, gC(k), 2 * ck, ck, C(k), 2 * ck, ck, net->slot(s, net->oU[kk]), D, pix, ck,
-                      GI_ACT_NONE, ds, &net->unorm[kk], need_wgrad, pend.planned ? &pend : nullptr));
-    pend = BwdFuse();
-    const void* Sin = (kk == nd) ? (const void*)net->slot(s, net->oE) : C(kk);
-    const int ca = net->up[kk].ca;
-    if (need_wgrad)
-      GI_TRY(wgrad(net, Sin, ca, ca, 0, kk < nd ? 1 : 0, D, ck, ck, 0, n, net->Hk[kk], net->Wk[kk], net->grads + net->up[kk].w_off));
-    void* gout = (kk == nd) ? (void*)net->shared(net->ogE) : gC(kk);
-    // the upper half of this GEMM's columns is the gradient at the output of the NEXT decoder level's BatchNorm (its ReLU is the
-    // consumer's): that layer's backward reduction rides in the epilogue (IgemmArgs::bwd_c0; levels without dropout, kernels that take it)
-    BwdFuse* pbf = nullptr;
-    const int kn = kk + 1;
-    if (kk <= nd - 1 && !(net->dropout_p > 0.f && !evalbn && kn >= 5 && kn <= nd - 1)) {
-      const int64_t pixn = (int64_t)n * net->Hk[kk] * net->Wk[kk];
-      pbf = &net->bwd_pending[net->unorm[kn].id];
-      *pbf = bwd_fuse_plan(net, s, net->unorm[kn], net->slot(s, net->oU[kn]), pixn, pixn / 256, 0.f);
-      pbf->c0 = ca / 2; pbf->c = ca / 2;
-    }
-    GI_TRY(igemm(net, 0, D, ck, ck, 0, packed_ptr(net, net->up[kk]), gout, ca, ca, 0, n, net->Hk[kk], net->Wk[kk], 0, GI_ACT_NONE,
-                 false, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr, 0, nullptr, nullptr, pbf));
-  }
   }  // decoder half
   if (phase == 1) return GI_OK;
   // the encoder half may be split once more: phase 3 = innermost .. level 5 (their parameter gradients, the bulk
@@ -1386,58 +1471,41 @@ int unet_backward(gi_net* net, int s, const float* dy, float* dx, int need_wgrad
   C1WFuse c1w;
   // innermost conv (no norm): dz = gE * [E > 0]
   if (run_inner) {
-    const int c = net->ch[nd];
-    const int64_t pix = (int64_t)n * net->Hk[nd] * net->Wk[nd];
+    const int c = net->ch[nd], cb = net->ch[nd - 1];
     D = side_dz(net);
-    GI_TRY(act_bn_bwd(net, s, nullptr, 0, 0, net->shared(net->ogE), c, 0, net->slot(s, net->oE), c, 0, nullptr, D, pix, c, GI_ACT_NONE,
-                      1.f, nullptr, need_wgrad));
-    const int cb = net->ch[nd - 1];
+    ActBnBwdArgs b = act_bwd_args(up_input(net, s, nd), (int64_t)n * net->Hk[nd] * net->Wk[nd], GI_ACT_NONE);
+    set_g2(b, sl(net->shared(net->ogE), c));
+    GI_TRY(act_bn_bwd(net, s, b, D));
     if (need_wgrad)
-      GI_TRY(wgrad(net, D, c, c, 0, 0, C(nd - 1), cb, 2 * cb, 0, n, net->Hk[nd], net->Wk[nd], net->grads + net->conv[nd].w_off));
-    GI_TRY(igemm(net, 1, D, c, c, 0, phase_ptr(net, net->conv[nd]), gA(nd - 1), cb, cb, 0, n, net->Hk[nd], net->Wk[nd], 0, GI_ACT_NONE,
-                 false, nullptr));
+      GI_TRY(wgrad_run(net, wgrad_args(net, sl(D, c), skip_half(net, s, nd - 1), n, net->Hk[nd], net->Wk[nd], net->grads + net->conv[nd].w_off)));
+    GI_TRY(gemm_run(net, 1, gemm_args(net, sl(D, c), phase_ptr(net, net->conv[nd]), sl(gA(nd - 1), cb), n, net->Hk[nd], net->Wk[nd])));
   }
   // encoder, innermost -> outermost
   for (int k = nd - 1; k >= 2; --k) {
     if (k >= 5 ? !run_inner : !run_outer) continue;
-    const int c = net->ch[k];
-    const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
+    const int c = net->ch[k], cb = net->ch[k - 1];
     D = side_dz(net);
-    GI_TRY(act_bn_bwd(net, s, gA(k), c, 0, gC(k), 2 * c, 0, C(k), 2 * c, 0, net->slot(s, net->oR[k]), D, pix, c, GI_ACT_LRELU, 1.f,
-                      &net->dnorm[k], need_wgrad));
-    const int cb = net->ch[k - 1];
+    ActBnBwdArgs b = act_bwd_args(skip_half(net, s, k), (int64_t)n * net->Hk[k] * net->Wk[k], GI_ACT_LRELU);
+    set_g1(b, sl(gA(k), c));
+    set_g2(b, sl(gC(k), c, 2 * c));
+    b.x = net->slot(s, net->oR[k]);
+    GI_TRY(act_bn_bwd(net, s, b, D, &net->dnorm[k], need_wgrad));
     if (need_wgrad)
-      GI_TRY(wgrad(net, D, c, c, 0, 0, C(k - 1), cb, 2 * cb, 0, n, net->Hk[k], net->Wk[k], net->grads + net->conv[k].w_off));
-    // d1 has no norm: its backward, (g + [y>0] * skip gradient) * LeakyReLU'(y), rides in the epilogue of d2's
-    // input-gradient GEMM when the kernel supports it (same arithmetic, one 4-tensor HBM pass less)
-    const bool fuse1 = (k == 2);
-    // ... and d1's weight gradient is formed from that GEMM's tiles while they are in LDS (IgemmArgs::c1w_*): the gradient at d1's
-    // output is never stored (the generator's input gradient is not asked for) and never read back
-    C1WFuse* pc1w = nullptr;
-    if (fuse1 && need_wgrad && net->oC1w >= 0 && gi_opt(GI_OPT_C1W_FUSE)) {
-      c1w.img = (const float*)net->slot(s, net->oX); c1w.part = (float*)net->shared(net->oC1w); c1w.part_floats = net->c1w_floats - 64 * 1024;
-      c1w.scale = iLS; c1w.skip_out = dx ? 0 : 1;
-      pc1w = &c1w;
+      GI_TRY(wgrad_run(net, wgrad_args(net, sl(D, c), skip_half(net, s, k - 1), n, net->Hk[k], net->Wk[k], net->grads + net->conv[k].w_off)));
+    Gemm g = gemm_args(net, sl(D, c), phase_ptr(net, net->conv[k]), sl(gA(k - 1), cb), n, net->Hk[k], net->Wk[k]);
+    if (k == 2) {   // d1's backward, (g + [y>0] * skip gradient) * LeakyReLU'(y), and its weight gradient ride in this GEMM where the kernel takes them
+      with_first_layer_bwd(net, s, g, skip_half(net, s, 1), need_wgrad, dx != nullptr, c1w);
+      g.a.add = gC(1); g.a.ldadd = 2 * cb;
     }
-    GI_TRY(igemm(net, 1, D, c, c, 0, phase_ptr(net, net->conv[k]), gA(k - 1), cb, cb, 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_NONE,
-                 false, nullptr, 0, fuse1 ? C(1) : nullptr, 2 * cb, 0.2f, fuse1 ? &lrelu1_done : nullptr, fuse1 ? gC(1) : nullptr, 2 * cb, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, (fuse1 && net->slot_bits1[s] && gi_opt(GI_OPT_MASK_BITS)) ? (const unsigned long long*)net->slot(s, net->oBits1) : nullptr,
-                 pc1w));
+    GI_TRY(gemm_run(net, 1, g));
+    if (k == 2) lrelu1_done = g.a.mask_applied;
   }
   if (run_outer) {
     const int c = net->ch[1];
-    const int64_t pix = (int64_t)n * net->Hk[1] * net->Wk[1];
-    void* D1 = D = side_dz(net);
-    if (lrelu1_done) D1 = gA(1);
-    else GI_TRY(act_bn_bwd(net, s, gA(1), c, 0, gC(1), 2 * c, 0, C(1), 2 * c, 0, nullptr, D, pix, c, GI_ACT_LRELU, 1.f, nullptr, need_wgrad));
-    if (need_wgrad && c1w.applied)
-      GI_TRY(op_c1_wgrad_reduce(st, c1w.part, net->grads + net->conv[1].w_off, c * 16, c1w.blocks, c1w.part + (int64_t)c1w.blocks * 1024,
-                                net->c1w_floats - (int64_t)c1w.blocks * 1024));
-    else if (need_wgrad)
-      GI_TRY(op_c1_wgrad(st, dt, D1, (const float*)net->slot(s, net->oX), net->grads + net->conv[1].w_off, n, net->Hk[1], net->Wk[1], c, c,
-                         0, 0, iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
-    if (dx) GI_TRY(op_c1_scatter(st, dt, D1, net->params + net->conv[1].w_off, nullptr, dx, n, net->Hk[1], net->Wk[1], c, c, 0, 0, 0, iLS,
-                                 net->shared(net->oCol)));
+    ActBnBwdArgs a1 = act_bwd_args(skip_half(net, s, 1), (int64_t)n * net->Hk[1] * net->Wk[1], GI_ACT_LRELU);
+    set_g1(a1, sl(gA(1), c));
+    set_g2(a1, sl(gC(1), c, 2 * c));
+    GI_TRY(first_layer_tail(net, s, net->conv[1], n, net->Hk[1], net->Wk[1], a1, need_wgrad, dx, lrelu1_done, &c1w));
   }
   return GI_OK;
 }
@@ -1451,168 +1519,112 @@ int unet_backward(gi_net* net, int s, const float* dy, float* dx, int need_wgrad
 int unet_forward_plain(gi_net* net, int s, const float* x, float* y, int n) {
   hipStream_t st = net->ctx->stream;
   const int nd = net->nd, dt = net->dtype, train = net->train;
-  const int H = net->H, W = net->W;
   net->slot_inference[s] = 0;
   net->slot_n[s] = n;
   net->slot_train[s] = train;
   net->slot_fused_u2[s] = 0;
-  auto C = [&](int k) { return (void*)net->slot(s, net->oC[k]); };
-  GI_HIP(hipMemcpyAsync(net->slot(s, net->oX), x, (size_t)n * H * W * 4, hipMemcpyDeviceToDevice, st));
-  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, C(1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
+  GI_TRY(input_copy(net, s, x, n));
+  GI_TRY(op_c1_gather(st, dt, x, net->params + net->conv[1].w_off, concat_buf(net, s, 1), n, net->Hk[1], net->Wk[1], net->ch[1], 2 * net->ch[1], 0,
                       GI_ACT_LRELU, 1.f, conv_bias(net, net->conv[1])));
-  for (int k = 2; k <= nd; ++k) {
-    if (k < nd) {
-      void* R = net->slot(s, net->oR[k]);
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, packed_ptr(net, net->conv[k]), R, net->ch[k], net->ch[k], 0, n,
-                   net->Hk[k], net->Wk[k], 0, GI_ACT_NONE, false, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr, 0, conv_bias(net, net->conv[k])));
-      GI_TRY(plain_norm_forward(net, s, net->dnorm[k], R, n, net->Hk[k] * net->Wk[k], C(k), 2 * net->ch[k], 0, GI_ACT_LRELU, nullptr, 1.f));
-    } else {
-      GI_TRY(igemm(net, 0, C(k - 1), net->ch[k - 1], 2 * net->ch[k - 1], 0, packed_ptr(net, net->conv[k]), net->slot(s, net->oE), net->ch[k],
-                   net->ch[k], 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_RELU, false, nullptr, 0, nullptr, 0, 0.f, nullptr, nullptr, 0,
-                   conv_bias(net, net->conv[k])));
-    }
+  for (int k = 2; k < nd; ++k) {
+    void* R = net->slot(s, net->oR[k]);
+    Gemm g = gemm_args(net, skip_half(net, s, k - 1), packed_ptr(net, net->conv[k]), sl(R, net->ch[k]), n, net->Hk[k], net->Wk[k]);
+    g.a.bias = conv_bias(net, net->conv[k]);
+    GI_TRY(gemm_run(net, 0, g));
+    GI_TRY(plain_norm_forward(net, s, net->dnorm[k], R, n, net->Hk[k] * net->Wk[k], skip_half(net, s, k), GI_ACT_LRELU));
+  }
+  {
+    Gemm g = gemm_args(net, skip_half(net, s, nd - 1), packed_ptr(net, net->conv[nd]), up_input(net, s, nd), n, net->Hk[nd], net->Wk[nd]);
+    g.a.act_out = GI_ACT_RELU; g.a.bias = conv_bias(net, net->conv[nd]);
+    GI_TRY(gemm_run(net, 0, g));
   }
   for (int k = nd; k >= 2; --k) {
-    const void* in = (k == nd) ? (const void*)net->slot(s, net->oE) : C(k);
-    const int cin = net->up[k].ca, co = net->ch[k - 1];
-    const int64_t opix = (int64_t)n * net->Hk[k - 1] * net->Wk[k - 1];
     void* U = net->slot(s, net->oU[k]);
-    const uint8_t* drop = nullptr;
-    if (train && net->dropout_p > 0.f && k >= 5 && k <= nd - 1) {
-      uint8_t* m = (uint8_t*)net->slot(s, net->oMask[k]);
-      if (net->ext_mask[s][k]) GI_TRY(op_mask_nchw_to_nhwc(st, net->ext_mask[s][k], m, n, co, net->Hk[k - 1] * net->Wk[k - 1], 1));
-      else GI_TRY(op_fill_dropout(st, m, opix * co, net->drop_seed + 0x1000003ull * (++net->drop_counter), net->dropout_p));
-      drop = m;
-    }
-    GI_TRY(igemm(net, 1, in, cin, cin, 0, phase_ptr(net, net->up[k]), U, co, co, 0, n, net->Hk[k], net->Wk[k], k < nd ? 1 : 0, GI_ACT_NONE,
-                 false, nullptr, k < nd ? net->ch[k] : 0, nullptr, 0, 0.f, nullptr, nullptr, 0, conv_bias(net, net->up[k])));
-    GI_TRY(plain_norm_forward(net, s, net->unorm[k], U, n, net->Hk[k - 1] * net->Wk[k - 1], C(k - 1), 2 * co, co, GI_ACT_RELU, drop,
-                              drop ? 1.f / (1.f - net->dropout_p) : 1.f));
+    Dropout drop;
+    GI_TRY(dropout_prepare(net, s, k, n, false, drop));
+    Gemm g = gemm_args(net, up_input(net, s, k), phase_ptr(net, net->up[k]), sl(U, net->ch[k - 1]), n, net->Hk[k], net->Wk[k]);
+    if (k < nd) { g.a.relu_in = 1; g.a.relu_cend = net->ch[k]; }
+    g.a.bias = conv_bias(net, net->up[k]);
+    GI_TRY(gemm_run(net, 1, g));
+    GI_TRY(plain_norm_forward(net, s, net->unorm[k], U, n, net->Hk[k - 1] * net->Wk[k - 1], up_half(net, s, k - 1), GI_ACT_RELU, drop));
   }
-  float* osave = (float*)net->slot(s, net->oOut);
-  if (net->out_c == 1)
-    return op_c1_scatter(st, dt, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, n, net->Hk[1], net->Wk[1],
-                         2 * net->ch[1], 2 * net->ch[1], 0, 1, 1, 1.f, net->shared(net->oCol), y);
-  const int c1 = 2 * net->ch[1];
-  if (op_c1_head4_ok(dt, c1, net->out_c, net->Wk[1], c1, 0))   // the face-parsing network's head: 64-row col GEMM + overlap-add
-    return op_c1_head4_forward(st, C(1), net->params + net->up[1].w_off, net->params + net->up[1].bias_off, osave, y, n, net->Hk[1], net->Wk[1], c1,
-                               0, 1, net->shared(net->oCol));
-  void* U1 = net->shared(net->oU1);
-  GI_TRY(igemm(net, 1, C(1), c1, c1, 0, net->shared(net->oUp1Phase), U1, 64, 64, 0, n, net->Hk[1], net->Wk[1], 1, GI_ACT_NONE, false, nullptr,
-               net->ch[1]));
-  const int64_t total = (int64_t)n * net->out_c * H * W;
-  if (dt == GI_F16)
-    hipLaunchKernelGGL(head_tanh_kernel<half_t>, dim3(grid1d(total)), dim3(256), 0, st, (const half_t*)U1, net->params + net->up[1].bias_off, osave,
-                       n, net->out_c, H * W);
-  else
-    hipLaunchKernelGGL(head_tanh_kernel<float>, dim3(grid1d(total)), dim3(256), 0, st, (const float*)U1, net->params + net->up[1].bias_off, osave, n,
-                       net->out_c, H * W);
-  GI_LAUNCH_CHECK();
-  GI_HIP(hipMemcpyAsync(y, osave, (size_t)n * net->out_c * H * W * 4, hipMemcpyDeviceToDevice, st));
-  return GI_OK;
+  return head_forward(net, s, y, n, true);
 }
 
-// backward of one normalisation step of the plain generator: dz of [dropout] -> activation, then through InstanceNorm
-int plain_norm_backward(gi_net* net, int s, const BN& b, const void* g1, int ldg1, const void* g2, int ldg2, int coffg2, const void* y, int ldy,
-                        int coffy, const void* x, void* dx, int n, int hw, int act, float drop_scale) {
-  if (net->norm_kind != 1)
-    return act_bn_bwd(net, s, g1, ldg1, 0, g2, ldg2, coffg2, y, ldy, coffy, nullptr, dx, (int64_t)n * hw, b.c, act, drop_scale, nullptr, 0);
-  ActBnBwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g1 = g1; a.ldg1 = ldg1; a.g2 = g2; a.ldg2 = ldg2; a.coffg2 = coffg2;
-  a.y = y; a.ldy = ldy; a.coffy = coffy; a.x = x; a.dx = dx;
-  a.pixels = (int64_t)n * hw; a.c = b.c; a.act = act; a.drop_scale = drop_scale;
+// backward of one normalisation step of the plain generator: dz of [dropout] -> activation, then through InstanceNorm (a: as for act_bn_bwd)
+int plain_norm_backward(gi_net* net, int s, const BN& b, ActBnBwdArgs a, void* dx, int n, int hw) {
+  if (net->norm_kind != 1) {
+    a.x = nullptr;   // no norm: nothing reads the raw tensor
+    return act_bn_bwd(net, s, a, dx);
+  }
+  a.dx = dx;
   return op_act_in_bwd(net->ctx->stream, net->dtype, a, n, hw, (const float*)net->slot(s, net->oInStats) + b.in_off);
 }
 
 int unet_backward_plain(gi_net* net, int s, const float* dy, float* dx, int need_wgrad, int phase) {
-  hipStream_t st = net->ctx->stream;
-  const int nd = net->nd, dt = net->dtype;
-  const int H = net->H, W = net->W, n = net->slot_n[s];
+  const int nd = net->nd, n = net->slot_n[s];
   GI_REQUIRE(n > 0, "unet_backward: slot %d holds no forward", s);
   GI_REQUIRE(net->out_c == 1 || !need_wgrad, "unet_backward: parameter gradients of a %d-channel generator are not built", net->out_c);
   net->bwd_eval = 0;
-  const float LS = net->loss_scale, iLS = 1.f / LS;
-  auto C = [&](int k) { return (void*)net->slot(s, net->oC[k]); };
   auto gC = [&](int k) { return (void*)net->shared(net->ogC[k]); };
   auto gA = [&](int k) { return (void*)net->shared(net->ogA[k]); };
   void* D = net->shared(net->oD);
-  float* G0 = (float*)net->shared(net->oG0);
-  const int64_t npx = (int64_t)n * H * W;
   const bool dropped = net->slot_train[s] && net->dropout_p > 0.f;
   if (phase == 0 || phase == 1) {
-    GI_TRY(op_tanh_bwd(st, dy, (const float*)net->slot(s, net->oOut), G0, npx * net->out_c, LS));
-    const int c1 = 2 * net->ch[1];
-    if (need_wgrad) {
-      hipLaunchKernelGGL(sum_part_kernel, dim3(256), dim3(256), 0, st, G0, npx, (double*)net->shared(net->oPart));
-      hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)net->shared(net->oPart), 256, net->grads + net->up[1].bias_off, iLS);
-      GI_LAUNCH_CHECK();
-      GI_TRY(op_c1_wgrad(st, dt, C(1), G0, net->grads + net->up[1].w_off, n, net->Hk[1], net->Wk[1], c1, c1, 0, 1, iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
-    }
-    if (net->out_c == 1) {
-      GI_TRY(op_c1_gather(st, dt, G0, net->params + net->up[1].w_off, gC(1), n, net->Hk[1], net->Wk[1], c1, c1, 0, GI_ACT_NONE, 1.f));
-    } else if (op_c1_head4_ok(dt, c1, net->out_c, net->Wk[1], c1, 0)) {
-      GI_TRY(op_c1_head4_dgrad(st, G0, net->params + net->up[1].w_off, gC(1), n, net->Hk[1], net->Wk[1], c1, 0));
-    } else {
-      void* U1 = net->shared(net->oU1);
-      if (dt == GI_F16) hipLaunchKernelGGL(pad_dy_kernel<half_t>, dim3(grid1d(npx * 64)), dim3(256), 0, st, G0, (half_t*)U1, n, net->out_c, H * W);
-      else hipLaunchKernelGGL(pad_dy_kernel<float>, dim3(grid1d(npx * 64)), dim3(256), 0, st, G0, (float*)U1, n, net->out_c, H * W);
-      GI_LAUNCH_CHECK();
-      const void* wp = net->oUp1Packed >= 0 ? (const void*)net->shared(net->oUp1Packed) : (const void*)net->shared(net->oUp1Pad);
-      GI_TRY(igemm(net, 0, U1, 64, 64, 0, wp, gC(1), c1, c1, 0, n, net->Hk[1], net->Wk[1], 0, GI_ACT_NONE, false, nullptr));
-    }
+    GI_TRY(head_backward(net, s, dy, need_wgrad));
     for (int k = 1; k <= nd - 1; ++k) {
-      const int kk = k + 1, ck = net->ch[k];
+      const int kk = k + 1, ck = net->ch[k], ca = net->up[kk].ca;
       const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
-      const float ds = (dropped && kk >= 5 && kk <= nd - 1) ? 1.f / (1.f - net->dropout_p) : 1.f;
-      GI_TRY(plain_norm_backward(net, s, net->unorm[kk], nullptr, 0, gC(k), 2 * ck, ck, C(k), 2 * ck, ck, net->slot(s, net->oU[kk]), D, n,
-                                 net->Hk[k] * net->Wk[k], GI_ACT_NONE, ds));
-      const void* Sin = (kk == nd) ? (const void*)net->slot(s, net->oE) : C(kk);
-      const int ca = net->up[kk].ca;
+      ActBnBwdArgs b = act_bwd_args(up_half(net, s, k), pix, GI_ACT_NONE);
+      set_g2(b, sl(gC(k), ck, 2 * ck, ck));
+      b.x = net->slot(s, net->oU[kk]);
+      if (dropped && kk >= 5 && kk <= nd - 1) b.drop_scale = 1.f / (1.f - net->dropout_p);
+      GI_TRY(plain_norm_backward(net, s, net->unorm[kk], b, D, n, net->Hk[k] * net->Wk[k]));
       if (need_wgrad) {
         GI_TRY(bias_grad(net, net->up[kk], D, pix, ck));
-        GI_TRY(wgrad(net, Sin, ca, ca, 0, kk < nd ? 1 : 0, D, ck, ck, 0, n, net->Hk[kk], net->Wk[kk], net->grads + net->up[kk].w_off));
+        WgradArgs wa = wgrad_args(net, up_input(net, s, kk), sl(D, ck), n, net->Hk[kk], net->Wk[kk], net->grads + net->up[kk].w_off);
+        wa.relu_S = kk < nd ? 1 : 0;
+        GI_TRY(wgrad_run(net, wa));
       }
       void* gout = (kk == nd) ? (void*)net->shared(net->ogE) : gC(kk);
-      GI_TRY(igemm(net, 0, D, ck, ck, 0, packed_ptr(net, net->up[kk]), gout, ca, ca, 0, n, net->Hk[kk], net->Wk[kk], 0, GI_ACT_NONE, false, nullptr));
+      GI_TRY(gemm_run(net, 0, gemm_args(net, sl(D, ck), packed_ptr(net, net->up[kk]), sl(gout, ca), n, net->Hk[kk], net->Wk[kk])));
     }
   }
   if (phase == 1) return GI_OK;
   const bool run_inner = phase != 4, run_outer = phase != 3;
   if (run_inner) {
-    const int c = net->ch[nd];
+    const int c = net->ch[nd], cb = net->ch[nd - 1];
     const int64_t pix = (int64_t)n * net->Hk[nd] * net->Wk[nd];
-    GI_TRY(act_bn_bwd(net, s, nullptr, 0, 0, net->shared(net->ogE), c, 0, net->slot(s, net->oE), c, 0, nullptr, D, pix, c, GI_ACT_NONE, 1.f,
-                      nullptr, need_wgrad));
-    const int cb = net->ch[nd - 1];
+    ActBnBwdArgs b = act_bwd_args(up_input(net, s, nd), pix, GI_ACT_NONE);
+    set_g2(b, sl(net->shared(net->ogE), c));
+    GI_TRY(act_bn_bwd(net, s, b, D));
     if (need_wgrad) {
       GI_TRY(bias_grad(net, net->conv[nd], D, pix, c));
-      GI_TRY(wgrad(net, D, c, c, 0, 0, C(nd - 1), cb, 2 * cb, 0, n, net->Hk[nd], net->Wk[nd], net->grads + net->conv[nd].w_off));
+      GI_TRY(wgrad_run(net, wgrad_args(net, sl(D, c), skip_half(net, s, nd - 1), n, net->Hk[nd], net->Wk[nd], net->grads + net->conv[nd].w_off)));
     }
-    GI_TRY(igemm(net, 1, D, c, c, 0, phase_ptr(net, net->conv[nd]), gA(nd - 1), cb, cb, 0, n, net->Hk[nd], net->Wk[nd], 0, GI_ACT_NONE, false, nullptr));
+    GI_TRY(gemm_run(net, 1, gemm_args(net, sl(D, c), phase_ptr(net, net->conv[nd]), sl(gA(nd - 1), cb), n, net->Hk[nd], net->Wk[nd])));
   }
   for (int k = nd - 1; k >= 2; --k) {
     if (k >= 5 ? !run_inner : !run_outer) continue;
-    const int c = net->ch[k];
+    const int c = net->ch[k], cb = net->ch[k - 1];
     const int64_t pix = (int64_t)n * net->Hk[k] * net->Wk[k];
-    GI_TRY(plain_norm_backward(net, s, net->dnorm[k], gA(k), c, gC(k), 2 * c, 0, C(k), 2 * c, 0, net->slot(s, net->oR[k]), D, n, net->Hk[k] * net->Wk[k],
-                               GI_ACT_LRELU, 1.f));
-    const int cb = net->ch[k - 1];
+    ActBnBwdArgs b = act_bwd_args(skip_half(net, s, k), pix, GI_ACT_LRELU);
+    set_g1(b, sl(gA(k), c));
+    set_g2(b, sl(gC(k), c, 2 * c));
+    b.x = net->slot(s, net->oR[k]);
+    GI_TRY(plain_norm_backward(net, s, net->dnorm[k], b, D, n, net->Hk[k] * net->Wk[k]));
     if (need_wgrad) {
       GI_TRY(bias_grad(net, net->conv[k], D, pix, c));
-      GI_TRY(wgrad(net, D, c, c, 0, 0, C(k - 1), cb, 2 * cb, 0, n, net->Hk[k], net->Wk[k], net->grads + net->conv[k].w_off));
+      GI_TRY(wgrad_run(net, wgrad_args(net, sl(D, c), skip_half(net, s, k - 1), n, net->Hk[k], net->Wk[k], net->grads + net->conv[k].w_off)));
     }
-    GI_TRY(igemm(net, 1, D, c, c, 0, phase_ptr(net, net->conv[k]), gA(k - 1), cb, cb, 0, n, net->Hk[k], net->Wk[k], 0, GI_ACT_NONE, false, nullptr));
+    GI_TRY(gemm_run(net, 1, gemm_args(net, sl(D, c), phase_ptr(net, net->conv[k]), sl(gA(k - 1), cb), n, net->Hk[k], net->Wk[k])));
   }
   if (run_outer) {
     const int c = net->ch[1];
-    const int64_t pix = (int64_t)n * net->Hk[1] * net->Wk[1];
-    GI_TRY(act_bn_bwd(net, s, gA(1), c, 0, gC(1), 2 * c, 0, C(1), 2 * c, 0, nullptr, D, pix, c, GI_ACT_LRELU, 1.f, nullptr, need_wgrad));
-    if (need_wgrad) {
-      GI_TRY(bias_grad(net, net->conv[1], D, pix, c));
-      GI_TRY(op_c1_wgrad(st, dt, D, (const float*)net->slot(s, net->oX), net->grads + net->conv[1].w_off, n, net->Hk[1], net->Wk[1], c, c, 0, 0, iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
-    }
-    if (dx) GI_TRY(op_c1_scatter(st, dt, D, net->params + net->conv[1].w_off, nullptr, dx, n, net->Hk[1], net->Wk[1], c, c, 0, 0, 0, iLS, net->shared(net->oCol)));
+    ActBnBwdArgs a1 = act_bwd_args(skip_half(net, s, 1), (int64_t)n * net->Hk[1] * net->Wk[1], GI_ACT_LRELU);
+    set_g1(a1, sl(gA(1), c));
+    set_g2(a1, sl(gC(1), c, 2 * c));
+    GI_TRY(first_layer_tail(net, s, net->conv[1], n, net->Hk[1], net->Wk[1], a1, need_wgrad, dx));
   }
   return GI_OK;
 }
@@ -1630,32 +1642,31 @@ int patchgan_forward(gi_net* net, int s, const float* x, float* y, int n) {
   net->slot_fused_u2[s] = fuse_a4 ? 1 : 0;   // (critic: "conv4's activation was not materialised")
   GI_TRY(op_c1_gather(st, dt, x, net->params + net->dconv[1].w_off, net->slot(s, net->oA[1]), n, H / 2, W / 2, 64, 64, 0, GI_ACT_LRELU, 1.f, nullptr,
                       gi_opt(GI_OPT_MASK_BITS) ? (unsigned long long*)net->slot(s, net->oBits1) : nullptr, &net->slot_bits1[s]));
-  // the copy of the input that conv1's weight gradient reads rides in conv2's normalisation pass where that pass takes a side
-  // copy (accumulator path); otherwise a device copy
   bool x_saved = false, a4_deferred = false;
   BnAccArgs a4_acc;
   for (int i = 2; i <= 4; ++i) {
     const Conv& c = net->dconv[i];
     const int Hs = H >> i, Ws = W >> i;
-    int nt = 0;
+    const int64_t pix = (int64_t)n * Hs * Ws;
     void* R = net->slot(s, net->oRd[i]);
-    StatPlan sp = stat_plan(net, net->dbn[i], (int64_t)n * Hs * Ws, ((int64_t)n * Hs * Ws + 127) / 128, train);
-    GI_TRY(igemm(net, 0, net->slot(s, net->oA[i - 1]), c.cb, c.cb, 0, packed_ptr(net, c), R, c.ca, c.ca, 0, n, Hs, Ws, 0, GI_ACT_NONE,
-                 true, &nt, 0, nullptr, 0, 0.f, nullptr, nullptr, 0, nullptr, &sp));
-    const bool side = i == 2 && sp.use && ((int64_t)n * H * W * 4) % 16 == 0;
+    StatPlan sp = stat_plan(net, net->dbn[i], pix, (pix + 127) / 128, train);
+    Gemm g = gemm_args(net, sl(net->slot(s, net->oA[i - 1]), c.cb), packed_ptr(net, c), sl(R, c.ca), n, Hs, Ws);
+    with_stats(net, g, sp);
+    GI_TRY(gemm_run(net, 0, g));
+    BnOpts o;
+    if (i == 2) o.side = input_side_copy(net, s, x, n, sp);
     // conv4 feeds only the head: its BatchNorm + LeakyReLU is applied by the head kernels from the raw tensor
     if (i == 4 && fuse_a4 && sp.use && gi_opt(GI_OPT_HEAD_FAST)) {   // the head's first kernel derives conv4's scale / shift itself (HeadArgs::bn)
-      a4_acc = bn_acc_args(net, s, net->dbn[i], sp, (int64_t)n * Hs * Ws / net->bn_groups, net->bn_groups);
+      a4_acc = bn_acc_args(net, s, net->dbn[i], sp, pix / net->bn_groups, net->bn_groups);
       bn_acc_commit(net, s, net->dbn[i], sp);
       a4_deferred = true;
       continue;
     }
-    GI_TRY(bn_forward(net, s, net->dbn[i], R, (int64_t)n * Hs * Ws, nt, net->slot(s, net->oA[i]), c.ca, 0, GI_ACT_LRELU, nullptr, 1.f, train,
-                      !(i == 4 && fuse_a4), &sp, 0.f, 0, side ? x : nullptr, side ? net->slot(s, net->oX) : nullptr,
-                      side ? (int64_t)n * H * W * 4 : 0));
-    if (side) x_saved = true;
+    o.apply = !(i == 4 && fuse_a4);
+    GI_TRY(bn_forward(net, s, net->dbn[i], R, pix, g.a.ntiles_out, sl(net->slot(s, net->oA[i]), c.ca), GI_ACT_LRELU, train, sp, o));
+    if (o.side.bytes > 0) x_saved = true;
   }
-  if (!x_saved) GI_HIP(hipMemcpyAsync(net->slot(s, net->oX), x, (size_t)n * H * W * 4, hipMemcpyDeviceToDevice, st));
+  if (!x_saved) GI_TRY(input_copy(net, s, x, n));
   HeadArgs h;
   h.a4 = net->slot(s, fuse_a4 ? net->oRd[4] : net->oA[4]);
   if (fuse_a4) {
@@ -1681,8 +1692,6 @@ int patchgan_backward(gi_net* net, int s, const float* dy, float* dx, int need_w
   GI_REQUIRE(net->slot_groups[s] == net->bn_groups, "patchgan_backward: slot %d was produced with %d BatchNorm groups, the net is set to %d", s,
              net->slot_groups[s], net->bn_groups);
   net->bwd_eval = 0;
-  const float LS = net->loss_scale, iLS = 1.f / LS;
-  void* D = net->shared(net->oD);
   HeadBwdArgs hb;
   hb.a4 = net->slot(s, net->oA[4]); hb.w5 = net->params + net->w5_off; hb.wl = net->params + net->wl_off;
   hb.h = (const float*)net->slot(s, net->oHh); hb.out = (const float*)net->slot(s, net->oOut);
@@ -1697,14 +1706,9 @@ int patchgan_backward(gi_net* net, int s, const float* dy, float* dx, int need_w
     hb.a4 = net->slot(s, net->oRd[4]);
     hb.scale4 = p.scale; hb.shift4 = p.shift; hb.n_per_group = n / net->bn_groups; hb.gstride = 4 * 512;
   }
-  hb.n = n; hb.Hh = net->Hh; hb.Wh = net->Wh; hb.c = 512; hb.sigmoid = net->sigmoid; hb.loss_scale = LS;
+  hb.n = n; hb.Hh = net->Hh; hb.Wh = net->Wh; hb.c = 512; hb.sigmoid = net->sigmoid; hb.loss_scale = net->loss_scale;
   if (phase != 2) {
-    // a reduction planned by an earlier, abandoned backward (phase 1 without its phase 2) left sums in its accumulator block
-    for (int i = 2; i <= 4; ++i) {
-      BwdFuse& pend = net->bwd_pending[net->dbn[i].id];
-      if (pend.planned) GI_HIP(hipMemsetAsync(pend.acc, 0, (size_t)net->dbn[i].acc_block() * 8, st));
-      pend = BwdFuse();
-    }
+    GI_TRY(clear_pending_bwd(net, &net->dbn[2], 3));
     // conv4's BatchNorm-backward sums ride in the head's input-gradient blocks (HeadBwdArgs::bwd_*): no reduce launch
     BwdFuse& p4 = net->bwd_pending[net->dbn[4].id];
     int head_bw = 0;
@@ -1719,57 +1723,36 @@ int patchgan_backward(gi_net* net, int s, const float* dy, float* dx, int need_w
   }
   int lrelu1_done = 0;
   C1WFuse c1w;
+  const Slice y1 = sl(net->slot(s, net->oA[1]), 64);
   for (int i = 4; i >= 2; --i) {
     if (i == 4 ? phase == 2 : phase == 1) continue;
     const Conv& c = net->dconv[i];
     const int Hs = H >> i, Ws = W >> i;
     const int64_t pix = (int64_t)n * Hs * Ws;
     BwdFuse& pend = net->bwd_pending[net->dbn[i].id];
-    D = side_dz(net);
-    GI_TRY(act_bn_bwd(net, s, net->shared(net->ogA[i]), c.ca, 0, nullptr, 0, 0, net->slot(s, net->oA[i]), c.ca, 0, net->slot(s, net->oRd[i]),
-                      D, pix, c.ca, GI_ACT_LRELU, 1.f, &net->dbn[i], need_wgrad, pend.planned ? &pend : nullptr));
+    void* D = side_dz(net);
+    ActBnBwdArgs b = act_bwd_args(sl(net->slot(s, net->oA[i]), c.ca), pix, GI_ACT_LRELU);
+    set_g1(b, sl(net->shared(net->ogA[i]), c.ca));
+    b.x = net->slot(s, net->oRd[i]);
+    GI_TRY(act_bn_bwd(net, s, b, D, &net->dbn[i], need_wgrad, &pend));
     pend = BwdFuse();
     if (need_wgrad)
-      GI_TRY(wgrad(net, D, c.ca, c.ca, 0, 0, net->slot(s, net->oA[i - 1]), c.cb, c.cb, 0, n, Hs, Ws, net->grads + c.w_off));
-    // conv1 has no BatchNorm: its LeakyReLU backward rides in the epilogue of conv2's input-gradient GEMM when the
-    // kernel supports it (same arithmetic, one 3-tensor HBM pass less)
-    const bool fuse1 = (i == 2);
-    // the gradient this GEMM produces enters BatchNorm + LeakyReLU of layer i - 1: its reduction rides in the GEMM's epilogue
-    BwdFuse* pbf = nullptr;
-    if (i >= 3) {
-      pbf = &net->bwd_pending[net->dbn[i - 1].id];
-      *pbf = bwd_fuse_plan(net, s, net->dbn[i - 1], net->slot(s, net->oRd[i - 1]), pix * 4, pix / 256 * 4, 0.2f);
+      GI_TRY(wgrad_run(net, wgrad_args(net, sl(D, c.ca), sl(net->slot(s, net->oA[i - 1]), c.cb), n, Hs, Ws, net->grads + c.w_off)));
+    Gemm g = gemm_args(net, sl(D, c.ca), phase_ptr(net, c), sl(net->shared(net->ogA[i - 1]), c.cb), n, Hs, Ws);
+    if (i >= 3) {   // the gradient this GEMM produces enters BatchNorm + LeakyReLU of layer i - 1: its reduction rides in the GEMM's epilogue
+      BwdFuse& bf = net->bwd_pending[net->dbn[i - 1].id];
+      bf = bwd_fuse_plan(net, s, net->dbn[i - 1], net->slot(s, net->oRd[i - 1]), pix * 4, pix / 256 * 4, 0.2f);
+      with_bn_bwd(g, bf);
+    } else {        // conv1 has no BatchNorm: its LeakyReLU backward and its weight gradient ride in this GEMM where the kernel takes them
+      with_first_layer_bwd(net, s, g, y1, need_wgrad, dx != nullptr, c1w);
     }
-    // ... and conv1's weight gradient is formed from that GEMM's tiles while they are in LDS (IgemmArgs::c1w_*); without an input
-    // gradient to compute, the gradient at conv1's output is never stored
-    C1WFuse* pc1w = nullptr;
-    if (fuse1 && need_wgrad && net->oC1w >= 0 && gi_opt(GI_OPT_C1W_FUSE)) {
-      c1w.img = (const float*)net->slot(s, net->oX); c1w.part = (float*)net->shared(net->oC1w); c1w.part_floats = net->c1w_floats - 64 * 1024;
-      c1w.scale = iLS; c1w.skip_out = dx ? 0 : 1;
-      pc1w = &c1w;
-    }
-    GI_TRY(igemm(net, 1, D, c.ca, c.ca, 0, phase_ptr(net, c), net->shared(net->ogA[i - 1]), c.cb, c.cb, 0, n, Hs, Ws, 0, GI_ACT_NONE, false,
-                 nullptr, 0, fuse1 ? net->slot(s, net->oA[1]) : nullptr, 64, 0.2f, fuse1 ? &lrelu1_done : nullptr, nullptr, 0, nullptr, nullptr, pbf, nullptr,
-                 nullptr, (fuse1 && net->slot_bits1[s] && gi_opt(GI_OPT_MASK_BITS)) ? (const unsigned long long*)net->slot(s, net->oBits1) : nullptr, pc1w));
+    GI_TRY(gemm_run(net, 1, g));
+    if (i == 2) lrelu1_done = g.a.mask_applied;
   }
   if (phase == 1) return GI_OK;
-  const int64_t pix = (int64_t)n * (H / 2) * (W / 2);
-  void* D1 = D = side_dz(net);
-  if (lrelu1_done) {
-    D1 = net->shared(net->ogA[1]);
-  } else {
-    GI_TRY(act_bn_bwd(net, s, net->shared(net->ogA[1]), 64, 0, nullptr, 0, 0, net->slot(s, net->oA[1]), 64, 0, nullptr, D, pix, 64, GI_ACT_LRELU,
-                      1.f, nullptr, need_wgrad));
-  }
-  if (need_wgrad && c1w.applied)
-    GI_TRY(op_c1_wgrad_reduce(st, c1w.part, net->grads + net->dconv[1].w_off, 64 * 16, c1w.blocks, c1w.part + (int64_t)c1w.blocks * 1024,
-                              net->c1w_floats - (int64_t)c1w.blocks * 1024));
-  else if (need_wgrad)
-    GI_TRY(op_c1_wgrad(st, dt, D1, (const float*)net->slot(s, net->oX), net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0, iLS, 1.f,
-                       nullptr, (float*)net->shared(net->oPart), net->part_floats));
-  if (dx) GI_TRY(op_c1_scatter(st, dt, D1, net->params + net->dconv[1].w_off, nullptr, dx, n, H / 2, W / 2, 64, 64, 0, 0, 0, iLS,
-                               net->shared(net->oCol)));
-  return GI_OK;
+  ActBnBwdArgs a1 = act_bwd_args(y1, (int64_t)n * (H / 2) * (W / 2), GI_ACT_LRELU);
+  set_g1(a1, sl(net->shared(net->ogA[1]), 64));
+  return first_layer_tail(net, s, net->dconv[1], n, H / 2, W / 2, a1, need_wgrad, dx, lrelu1_done, &c1w);
 }
 
 }  // namespace
@@ -1835,9 +1818,11 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
     const int Hs = H >> i, Ws = W >> i;
     const int64_t pix = (int64_t)n * Hs * Ws, cnt = pix * c.ca;
     void* TX = net->shared(net->oTX[i]);
-    GI_TRY(igemm(net, 0, A2(i - 1, 0), c.cb, c.cb, 0, packed_ptr(net, c), TX, c.ca, c.ca, 0, n, Hs, Ws, 0, GI_ACT_NONE, false, nullptr));
-    GI_TRY(act_bn_bwd(net, s, TX, c.ca, 0, nullptr, 0, 0, TX, c.ca, 0, net->slot(s, net->oRd[i]), TZ, pix, c.ca, GI_ACT_NONE, 1.f,
-                      &net->dbn[i], 0));   // BatchNorm Jacobian applied to the tangent
+    GI_TRY(gemm_run(net, 0, gemm_args(net, sl(A2(i - 1, 0), c.cb), packed_ptr(net, c), sl(TX, c.ca), n, Hs, Ws)));
+    ActBnBwdArgs jt = act_bwd_args(sl(TX, c.ca), pix, GI_ACT_NONE);   // BatchNorm Jacobian applied to the tangent
+    set_g1(jt, sl(TX, c.ca));
+    jt.x = net->slot(s, net->oRd[i]);
+    GI_TRY(act_bn_bwd(net, s, jt, TZ, &net->dbn[i]));
     GI_TRY(op_mul_slope(st, dt, TZ, net->slot(s, net->oA[i]), A2(i, 0), cnt));
     GI_HIP(hipMemcpyAsync(A2(i, 1), net->slot(s, net->oA[i]), cnt * T, hipMemcpyDeviceToDevice, st));
   }
@@ -1861,25 +1846,29 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
     const int Hs = H >> i, Ws = W >> i;
     const int64_t pix = (int64_t)n * Hs * Ws, half = pix * c.ca * T;
     // tangent-gradient chain: d(tx_i) = J_BN( slope * d(ta_i) )
-    GI_TRY(act_bn_bwd(net, s, G2(i, 0), c.ca, 0, nullptr, 0, 0, net->slot(s, net->oA[i]), c.ca, 0, net->slot(s, net->oRd[i]), D2, pix, c.ca,
-                      GI_ACT_LRELU, 1.f, &net->dbn[i], 0));
+    ActBnBwdArgs b = act_bwd_args(sl(net->slot(s, net->oA[i]), c.ca), pix, GI_ACT_LRELU);
+    set_g1(b, sl(G2(i, 0), c.ca));
+    b.x = net->slot(s, net->oRd[i]);
+    GI_TRY(act_bn_bwd(net, s, b, D2, &net->dbn[i]));
     // primal chain: standard BatchNorm backward of the gradient arriving from the layer above (dgamma / dbeta: s * L, 1/L removed)
-    GI_TRY(act_bn_bwd(net, s, G2(i, 1), c.ca, 0, nullptr, 0, 0, net->slot(s, net->oA[i]), c.ca, 0, net->slot(s, net->oRd[i]), D2 + half, pix,
-                      c.ca, GI_ACT_LRELU, 1.f, &net->dbn[i], 1));
+    set_g1(b, sl(G2(i, 1), c.ca));
+    GI_TRY(act_bn_bwd(net, s, b, D2 + half, &net->dbn[i], 1));
     // dependence of the BatchNorm Jacobian on the primal input (dgamma: s * L, 1/L removed here)
     BNPtrs bp = bn_ptrs(net, s, net->dbn[i]);
     GI_TRY(op_bn_tangent_inject(st, dt, G2(i, 0), net->slot(s, net->oA[i]), net->shared(net->oTX[i]), net->slot(s, net->oRd[i]), D2 + half, pix,
                                 c.ca, net->params + net->dbn[i].gamma_off, bp.mean, bp.inv, net->grads + net->dbn[i].gamma_off, iLS,
                                 (float*)net->shared(net->oGPpart), (float*)net->shared(net->oGPsums)));
     // conv_i on the stacked 2n batch: [d(tx_i); dxp_i] x [ta_{i-1}; a_{i-1}] (both products s * L; wgrad removes L)
-    GI_TRY(wgrad(net, D2, c.ca, c.ca, 0, 0, A2(i - 1, 0), c.cb, c.cb, 0, 2 * n, Hs, Ws, net->grads + c.w_off));
-    GI_TRY(igemm(net, 1, D2, c.ca, c.ca, 0, phase_ptr(net, c), G2(i - 1, 0), c.cb, c.cb, 0, 2 * n, Hs, Ws, 0, GI_ACT_NONE, false, nullptr));
+    GI_TRY(wgrad_run(net, wgrad_args(net, sl(D2, c.ca), sl(A2(i - 1, 0), c.cb), 2 * n, Hs, Ws, net->grads + c.w_off)));
+    GI_TRY(gemm_run(net, 1, gemm_args(net, sl(D2, c.ca), phase_ptr(net, c), sl(G2(i - 1, 0), c.cb), 2 * n, Hs, Ws)));
   }
   {
     const int64_t pix = (int64_t)n * (H / 2) * (W / 2), half = pix * 64 * T;
-    GI_TRY(act_bn_bwd(net, s, G2(1, 0), 64, 0, nullptr, 0, 0, net->slot(s, net->oA[1]), 64, 0, nullptr, D2, pix, 64, GI_ACT_LRELU, 1.f, nullptr, 0));
-    GI_TRY(act_bn_bwd(net, s, G2(1, 1), 64, 0, nullptr, 0, 0, net->slot(s, net->oA[1]), 64, 0, nullptr, D2 + half, pix, 64, GI_ACT_LRELU, 1.f,
-                      nullptr, 0));
+    ActBnBwdArgs b = act_bwd_args(sl(net->slot(s, net->oA[1]), 64), pix, GI_ACT_LRELU);
+    set_g1(b, sl(G2(1, 0), 64));
+    GI_TRY(act_bn_bwd(net, s, b, D2));
+    set_g1(b, sl(G2(1, 1), 64));
+    GI_TRY(act_bn_bwd(net, s, b, D2 + half));
     // conv1: tangent half against v * s (L * s), primal half against xhat (s * L)
     GI_TRY(op_c1_wgrad(st, dt, D2, vimg, net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0, iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
     GI_TRY(op_c1_wgrad(st, dt, D2 + half, (const float*)net->slot(s, net->oX), net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0,
