@@ -58,12 +58,16 @@ __device__ __forceinline__ void bn_from_acc(const BnAccP& a, int c, int ch, int 
   }
 }
 
-// dropout keep-mask of element i under `seed` (splitmix64 of a counter), keep with probability 1 - p
-__device__ __forceinline__ uint8_t dropout_keep(uint64_t seed, int64_t i, uint32_t thresh) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);
+// the splitmix64 finaliser: the hash behind every counter-based draw of the library (dropout below, maskgen.hip)
+__host__ __device__ __forceinline__ uint64_t gi_mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
+  return z ^ (z >> 31);
+}
+constexpr uint64_t GI_GOLDEN64 = 0x9E3779B97F4A7C15ull;   // the counter's stride
+// dropout keep-mask of element i under `seed` (splitmix64 of a counter), keep with probability 1 - p
+__device__ __forceinline__ uint8_t dropout_keep(uint64_t seed, int64_t i, uint32_t thresh) {
+  const uint64_t z = gi_mix64(seed + GI_GOLDEN64 * (uint64_t)(i + 1));
   return ((uint32_t)(z >> 32) >= thresh) ? 1 : 0;
 }
 static inline uint32_t gi_dropout_thresh(float p) {   // keep when the 32-bit draw >= thresh

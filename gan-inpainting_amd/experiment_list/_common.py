@@ -92,6 +92,39 @@ def to_device_images(t, device, state):
     return t.float().contiguous()
 
 
+def to_device_mask(item, like, device, state, split, epoch):
+    """A loader's mask item -> (n,1,h,w) float32 on the device. Row ids (int64 (n,): datasets with masks="generated") become the masks
+    of --masks rect / freeform (lib/data/masks.py), sized like the batch's images `like` and keyed by (split, epoch, row): the
+    training split's change per epoch, every other split's do not. Mask pixels (float, uint8) take to_device_images."""
+    from ..lib.data import masks as M
+    if not M.is_key_item(item):
+        return to_device_images(item, device, state)
+    kind = state.get("masks", "files")
+    if kind not in M.KINDS:
+        raise ValueError(f"the loader yields row ids instead of masks, which needs --masks rect or freeform (got {kind!r})")
+    h, w = int(like.shape[-2]), int(like.shape[-1])
+    gens = state.setdefault("_mask_generators", {})
+    gen = gens.get((h, w))
+    if gen is None:
+        gen = gens[(h, w)] = M.DeviceMaskGenerator(kind, h, w, state.get("mask_seed", 0))
+    return gen(M.mask_key(split, epoch, item).to(device, non_blocking=True))
+
+
+def eval_prepare(state, device, split, epoch):
+    """The `prepare` of evaluate.calculate_metric for one loader: it is applied to the images, then to the mask item of the same batch."""
+    last = {}
+
+    def prep(t):
+        from ..lib.data.masks import is_key_item
+        if is_key_item(t):
+            if "images" not in last:
+                raise RuntimeError("eval_prepare: a batch's row ids arrived before its images (calculate_metric prepares the images first)")
+            return to_device_mask(t, last.pop("images"), device, state, split, epoch)
+        last["images"] = to_device_images(t, device, state)
+        return last["images"]
+    return prep
+
+
 def _fid_stats(state, mode):
     """state["train_fid"] / state["test_fid"] (train.py:177-178), or the reference's "not computed" pair."""
     st = state.get(mode + "_fid")
@@ -122,7 +155,7 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
             acc_d = [torch.zeros(len(f.names), device=device) for f in flows_D]
         for bi, (ground, mask, extra) in enumerate(loaders["train"]):
             ground = to_device_images(ground, device, state)
-            mask = to_device_images(mask, device, state)
+            mask = to_device_mask(mask, ground, device, state, "train", epoch)
             if pass_extra:
                 L, g_updated = batch_fn(bi, ground, mask, extra.to(device, non_blocking=True).contiguous())
             else:
@@ -160,9 +193,9 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
             if state.get("eval_fn"):
                 eval_hist.append(state["eval_fn"](net_G, loaders.get("test"), epoch))
             else:                                                # minimaxgan_l1.py:235-240
-                prep = lambda t: to_device_images(t, device, state)   # noqa: E731
                 rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
-                                                         inception_model=state.get("inception_model"), epoch=epoch, prepare=prep)
+                                                         inception_model=state.get("inception_model"), epoch=epoch,
+                                                         prepare=eval_prepare(state, device, k, epoch))
                             for k in ("train", "test") if loaders.get(k) is not None}
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))

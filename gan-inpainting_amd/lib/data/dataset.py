@@ -23,9 +23,13 @@ def pil_loader(path):
 class InpaintingDataset(torch.utils.data.Dataset):
     """dataset.py:14-51. Rows supply groundtruth_source, mask_source and (optional) segment (.npy label map).
     Returns (groundtruth, mask, segment): with transform=None the two images are uint8 (H, W) tensors for the
-    device transform; a host transform (callable on PIL images) is applied like the reference does."""
+    device transform; a host transform (callable on PIL images) is applied like the reference does.
+    masks="generated" (an extension, lib/data/masks.py): the mask_source column is neither required nor read and the
+    second item is the sample's row id, a 0-d int64 - the `_row` column when the frame has one (train.py numbers the
+    rows before it shards them, so the ids are global), else the index - which the training loop turns into a mask
+    on the device."""
 
-    def __init__(self, root, dataframe=None, csv_file=None, transform=None):
+    def __init__(self, root, dataframe=None, csv_file=None, transform=None, masks="files"):
         if dataframe is not None:
             self.image_df = dataframe
         elif csv_file:
@@ -33,8 +37,11 @@ class InpaintingDataset(torch.utils.data.Dataset):
             self.image_df = pd.read_csv(csv_file)
         else:
             raise Exception("Please supply dataframe or file path")
+        if masks not in ("files", "generated"):
+            raise ValueError(f"masks={masks!r} (files or generated)")
         self.transform = transform
         self.root = root
+        self.masks = masks
 
     def __len__(self):
         return len(self.image_df)
@@ -42,16 +49,21 @@ class InpaintingDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         rows = self.image_df.iloc[idx]
         groundtruth = pil_loader(os.path.join(self.root, rows["groundtruth_source"]))
-        mask = pil_loader(os.path.join(self.root, rows["mask_source"]))
+        generated = self.masks == "generated"
+        if generated:
+            mask = torch.tensor(int(rows["_row"]) if "_row" in rows else int(idx), dtype=torch.int64)
+        else:
+            mask = pil_loader(os.path.join(self.root, rows["mask_source"]))
         if "segment" in rows and isinstance(rows["segment"], str) and rows["segment"]:
             segment = torch.from_numpy(np.load(os.path.join(self.root, rows["segment"])))
         else:
             segment = torch.zeros((1,), dtype=torch.long)
         if self.transform:
-            groundtruth, mask = self.transform(groundtruth), self.transform(mask)
+            groundtruth = self.transform(groundtruth)
+            mask = mask if generated else self.transform(mask)
         else:
             groundtruth = torch.from_numpy(np.asarray(groundtruth, dtype=np.uint8).copy())
-            mask = torch.from_numpy(np.asarray(mask, dtype=np.uint8).copy())
+            mask = mask if generated else torch.from_numpy(np.asarray(mask, dtype=np.uint8).copy())
         return groundtruth, mask, segment
 
 

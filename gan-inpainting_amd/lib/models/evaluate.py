@@ -62,7 +62,7 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         stats = fid_score.FidStats(inception_model.flat.device, 2048)
     for inp, mask, *_ in loader:
         if prepare is not None:
-            inp, mask = prepare(inp), prepare(mask)
+            inp, mask = prepare(inp), prepare(mask)     # images first: a prepare that generates masks sizes them like the batch's images
         else:
             inp = inp.to(device, non_blocking=True).float().contiguous()
             mask = mask.to(device, non_blocking=True).float().contiguous()

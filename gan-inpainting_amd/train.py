@@ -24,10 +24,13 @@ if ROOT not in sys.path:
 
 
 class SyntheticInpainting(torch.utils.data.Dataset):
-    """(groundtruth, mask, segment) triples like lib/data/dataset.py:35-51, synthetic content."""
+    """(groundtruth, mask, segment) triples like lib/data/dataset.py:35-51, synthetic content. masks="generated": the second item
+    is the row id row0 + i (a 0-d int64) instead of a rectangle drawn on the host; the loop generates the mask on the device."""
 
-    def __init__(self, n, size, seed):
-        self.n, self.size, self.seed = n, size, seed
+    def __init__(self, n, size, seed, masks="host", row0=0):
+        if masks not in ("host", "generated"):
+            raise ValueError(f"masks={masks!r} (host or generated)")
+        self.n, self.size, self.seed, self.masks, self.row0 = n, size, seed, masks, row0
 
     def __len__(self):
         return self.n
@@ -36,15 +39,23 @@ class SyntheticInpainting(torch.utils.data.Dataset):
         g = torch.Generator().manual_seed(self.seed + i)
         s = self.size
         ground = torch.rand((1, s, s), generator=g)
+        if self.masks == "generated":
+            mask = torch.tensor(self.row0 + i, dtype=torch.int64)
+        else:
+            mask = self._host_rectangle(s, g)
+        coarse = torch.randint(0, 4, ((s + 7) // 8, (s + 7) // 8), generator=g)          # blocky 4-class face-parsing labels
+        segment = coarse.repeat_interleave(8, 0).repeat_interleave(8, 1)[:s, :s].contiguous()
+        return ground, mask, segment
+
+    @staticmethod
+    def _host_rectangle(s, g):
         h = int(torch.randint(s // 8, s // 2 + 1, (1,), generator=g))
         w = int(torch.randint(s // 8, s // 2 + 1, (1,), generator=g))
         y0 = int(torch.randint(0, s - h + 1, (1,), generator=g))
         x0 = int(torch.randint(0, s - w + 1, (1,), generator=g))
         mask = torch.zeros((1, s, s))
         mask[0, y0:y0 + h, x0:x0 + w] = 1.0
-        coarse = torch.randint(0, 4, ((s + 7) // 8, (s + 7) // 8), generator=g)          # blocky 4-class face-parsing labels
-        segment = coarse.repeat_interleave(8, 0).repeat_interleave(8, 1)[:s, :s].contiguous()
-        return ground, mask, segment
+        return mask
 
 
 def shard_rows(df, rank, world, batchsize):
@@ -55,6 +66,19 @@ def shard_rows(df, rank, world, batchsize):
         raise ValueError(f"{len(df)} rows cannot fill one batch of {batchsize} on each of {world} ranks (every rank would run zero batches "
                          f"per epoch): lower --batchsize or the number of ranks")
     return df.iloc[:keep].iloc[rank::world].reset_index(drop=True)
+
+
+def load_rows(csv_path, rank, world, batchsize):
+    """The rows of one CSV for this rank, numbered in a `_row` column BEFORE they are sharded: the ids are global, so a mask
+    generated from one (--masks rect / freeform) does not depend on the world size."""
+    import pandas as pd
+    df = pd.read_csv(csv_path)
+    df["_row"] = range(len(df))
+    if world > 1:
+        # every rank must see the same number of batches (each optimizer update holds an all-reduce): cut the
+        # index to a multiple of world * batchsize, then one interleaved shard per rank
+        df = shard_rows(df, rank, world, batchsize)
+    return df
 
 
 def build_parser():
@@ -85,6 +109,11 @@ def build_parser():
                         help="local path of the published FID Inception state dict (pt_inception-2015-12-05-*.pth); enables FID in the "
                              "evaluation pass (train.py:154-180). Nothing is ever downloaded; without the flag fid stays -1")
     parser.add_argument("--data", default="synthetic")
+    parser.add_argument("--masks", choices=["files", "rect", "freeform"], default="files",
+                        help="files: the masks the data supplies (the mask_source files of --data <dir>; host rectangles for "
+                             "--data synthetic). rect / freeform: generated on the device per sample (lib/data/masks.py): "
+                             "the CSVs need no mask_source column, test masks are the same in every epoch, training masks change")
+    parser.add_argument("--mask-seed", dest="mask_seed", type=int, default=0, help="seed of the generated masks")
     parser.add_argument("--samples", type=int, default=1024)
     parser.add_argument("--outdir", default=os.path.join(os.getcwd(), "runs"))
     parser.add_argument("--perceptual-grad", dest="perceptual_grad", action="store_true", default=False,
@@ -105,26 +134,24 @@ def main(argv=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(parallel.local_device())
     lkw = {"num_workers": args.workers}
+    generated = args.masks != "files"
     if args.workers > 0:
         lkw.update(persistent_workers=True, pin_memory=True, prefetch_factor=4)
     if args.data != "synthetic":
         # the reference's dataset layout (train.py:64-90): <dir>/csv/{train,test}_all_masks.csv with columns
         # groundtruth_source, mask_source[, segment]; decode on the host, Resize + ToTensor on the device
-        import pandas as pd
         from gan_inpainting_amd.lib.data import dataset
 
         def mk_real(csv, shuffle):
-            df = pd.read_csv(os.path.join(args.data, "csv", csv))
-            if world > 1:
-                # every rank must see the same number of batches (each optimizer update holds an all-reduce): cut the
-                # index to a multiple of world * batchsize, then one interleaved shard per rank
-                df = shard_rows(df, rank, world, args.batchsize)
-            return torch.utils.data.DataLoader(dataset.InpaintingDataset(args.data, dataframe=df, transform=None),
+            df = load_rows(os.path.join(args.data, "csv", csv), rank, world, args.batchsize)
+            return torch.utils.data.DataLoader(dataset.InpaintingDataset(args.data, dataframe=df, transform=None,
+                                                                         masks="generated" if generated else "files"),
                                                batch_size=args.batchsize, shuffle=shuffle, drop_last=True, **lkw)
         loaders = {"train": mk_real("train_all_masks.csv", True), "test": mk_real("test_all_masks.csv", True)}     # :75-90
     else:
         mk = lambda n, seed: torch.utils.data.DataLoader(   # noqa: E731
-            SyntheticInpainting(n, args.imagedim, seed + 100000 * rank), batch_size=args.batchsize, shuffle=True, drop_last=True, **lkw)
+            SyntheticInpainting(n, args.imagedim, seed + 100000 * rank, masks="generated" if generated else "host", row0=rank * n),
+            batch_size=args.batchsize, shuffle=True, drop_last=True, **lkw)
         loaders = {"train": mk(args.samples, 1), "test": mk(max(args.batchsize, 64), 2), "extra": mk(max(args.batchsize, 64), 3)}
     segmentation_model = None
     if args.face_parsing == "random":
@@ -133,6 +160,7 @@ def main(argv=None):
         torch.manual_seed(20240)
         segmentation_model = networks.UnetGenerator(1, 4, 7, ngf=32, norm_layer=functools.partial(torch.nn.BatchNorm2d, affine=True,
                                                     track_running_stats=True), use_dropout='False', dtype=args.dtype).eval()   # train.py:171-175
+    state.update({"masks": args.masks, "mask_seed": args.mask_seed})
     state.update({"train_fid": None, "test_fid": None, "inception_model": None, "segmentation_model": segmentation_model})
     if args.fid_weights:
         # train.py:154-180: ground-truth statistics of the train and test loaders, once. Every rank computes them on its own shard

@@ -447,6 +447,20 @@ int gi_resize_build_tables(gi_ctx* ctx, int in_h, int in_w, int out_h, int out_w
 int gi_resize_to_tensor(gi_ctx* ctx, const void* tables_dev, const uint8_t* src, int n, int in_h, int in_w,
                         int out_h, int out_w, float* dst_f32, uint8_t* dst_u8, uint8_t* tmp);
 
+/* ---- device mask generator (NOT in the reference, whose masks are files): the hole masks of a batch
+ *      as a pure integer function of (kind, seed, key, H, W) - not of the batch, the image's place in it or n.
+ *      Counter-based draws on the dropout hash: stream = mix(seed + G*(key+1)), draw(k) = mix(stream + G*(k+1)) >> 32,
+ *      uni(k, lo, hi) = lo + ((draw(k) * (hi-lo+1)) >> 32). kind 0: one rectangle, h = uni(0, H/8, H/2), w = uni(1, W/8, W/2),
+ *      y0 = uni(2, 0, H-h), x0 = uni(3, 0, W-w) (the benchmark's distribution). kind 1: the union of 2..5 thick polylines of
+ *      3..11 segments each (at most 55 capsules, exact integer point-in-capsule test); DESIGN 4.1e-2 is the normative text
+ *      and tests/maskgen_ref.py its numpy restatement, bit-exact with this entry.
+ *      keys_dev: n int64 on the device; mask_out: (n,1,H,W) fp32 of {0,1}, 4-byte aligned; coverage_out (may be NULL):
+ *      n ints, the number of ones per image (zeroed by the call, integer adds: deterministic). 16 <= H, W <= 4096, any
+ *      value in between; n > 0. Invalid arguments return GI_ERR_INVALID before anything is launched; asynchronous on
+ *      the context's stream. */
+int gi_mask_generate(gi_ctx* ctx, int kind, uint64_t seed, const int64_t* keys_dev, int n, int H, int W, float* mask_out,
+                     int* coverage_out);
+
 /* ---- single-layer entry points (unit parity tests and kernel roofline measurements) -------- */
 /* out[n,y,x,a] = act( sum_{ky,kx,b} in[n,2y-1+ky,2x-1+kx,b] * w[a][ky][kx][b] ), NHWC, dtype T.
  * in: (n,H,W,cb) ld=ldin; out: (n,H/2,W/2,ca) ld=ldout. w_packed is T [ca][16*cb].
