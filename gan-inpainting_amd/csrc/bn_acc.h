@@ -1,5 +1,5 @@
 // BatchNorm from the exact accumulators (stat_acc.h): the pieces shared by the normalisation pass (elementwise.hip), the kernels that
-// apply the affine map themselves (c1.hip) and the GEMM that normalises its own output (igemm7.hip, IgemmFold).
+// apply the affine map themselves (c1.hip, head.hip) and the GEMM that normalises its own output (igemm7.hip, IgemmFold).
 #pragma once
 #include "common.h"
 #include "stat_acc.h"

@@ -258,6 +258,140 @@ __global__ void __launch_bounds__(256) c1_gather_mfma_kernel(const float* __rest
   }
 }
 
+// ---- the col step and the overlap-add, shared --------------------------------------------------------------------------------------
+// One copy of what c1_col_kernel and c1_scatter_fused_kernel (the col step) and the three overlap-adding kernels share: the fused
+// launch gives the bits of the two-launch form because it runs the same code. Lane (tapr, kq) = (lane & 15, lane >> 4): tapr is the A
+// row (tap) and the B column (pixel of the group), kq the 8-channel chunk of a 32-channel K step.
+// c1_col_load and c1_overlap_add return BY VALUE on purpose (through references the loads were scheduled worse).
+
+// A fragments: af[ks][j] = w[channel ks * 32 + kq * 8 + j][tap tapr]
+template <int KS>
+__device__ __forceinline__ void c1_col_afrag(const float* w, int tapr, int kq, h8_t (&af)[KS]) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) af[ks][j] = (half_t)w[(ks * 32 + kq * 8 + j) * 16 + tapr];
+}
+
+// raw B operand of pixel pix, K step ks: this lane's 16-byte piece, from X2 for the upper half of the channels when there is one; zeros
+// where the pixel is not live (no load)
+template <int KS>
+__device__ __forceinline__ h8_t c1_col_load(const char* X, const char* X2, int64_t pix, bool live, int ldx, int coffx, int ld2, int kq, int ks) {
+  constexpr int KH = KS / 2;
+  const h8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (X2 && ks >= KH) return live ? *(const h8_t*)(X2 + ((pix * ld2 + (ks - KH) * 32 + kq * 8) << 1)) : zero;
+  return live ? *(const h8_t*)(X + ((pix * ldx + coffx + ks * 32 + kq * 8) << 1)) : zero;
+}
+
+// s2 / h2 of this lane's upper-half channels: from sc2 / sh2, or (use_fa) derived by every workgroup from the layer's exact accumulators
+// into aff ([2][KH * 32] floats of LDS); workgroup 0 publishes them and clears the layer's other accumulator region. Called by ALL threads
+// of the workgroup under kernel-uniform conditions only: the use_fa side holds a __syncthreads().
+// aff MUST point into LDS (the callers cast their __shared__ array / dynamic-LDS tail): typed so, its reads stay LDS reads
+typedef __attribute__((address_space(3))) float lds_float_t;
+template <int KH>
+__device__ __forceinline__ void c1_upper_coefs(lds_float_t* aff, const BnAccP& fa, int use_fa, const float* sc2, const float* sh2, int kq,
+                                               float (&s2)[KH][8], float (&h2)[KH][8]) {
+  if (use_fa) {
+    if (threadIdx.x < KH * 32) {
+      float a, b;
+      bn_from_acc(fa, KH * 32, threadIdx.x, 0, blockIdx.x == 0, a, b);
+      aff[threadIdx.x] = a;
+      aff[KH * 32 + threadIdx.x] = b;
+    }
+    if (blockIdx.x == 0 && fa.zero_next) zero_words64(fa.zero_next, fa.zero_words);
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < KH; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s2[ks][j] = aff[ks * 32 + kq * 8 + j]; h2[ks][j] = aff[KH * 32 + ks * 32 + kq * 8 + j]; }
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < KH; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s2[ks][j] = sc2[ks * 32 + kq * 8 + j]; h2[ks][j] = sh2[ks * 32 + kq * 8 + j]; }
+  }
+}
+
+// the upper-half transform of 8 channels: relu(fma(x, s, h)) in fp32, ONE rounding to fp16 (the separate apply pass's expression).
+// Also the X2 side of c1_wgrad_mfma_kernel.
+__device__ __forceinline__ h8_t c1_upper8(h8_t raw, const float (&s)[8], const float (&h)[8]) {
+  h8_t o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float t = fmaf((float)raw[j], s[j], h[j]);
+    o[j] = (half_t)(t > 0.f ? t : 0.f);
+  }
+  return o;
+}
+
+// B fragments from the raw pieces: lower half relu?(x), upper half (has_x2) through c1_upper8, zero where the pixel is not live (raw is
+// zero there, relu(fma(0, s, h)) is not)
+template <int KS>
+__device__ __forceinline__ void c1_col_bfrag(const h8_t (&raw)[KS], bool has_x2, int relu_in, bool live, const float (&s2)[KS / 2][8],
+                                             const float (&h2)[KS / 2][8], h8_t (&bf)[KS]) {
+  constexpr int KH = KS / 2;
+  const h8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    if (has_x2 && ks >= KH) {
+      const h8_t u = c1_upper8(raw[ks], s2[ks >= KH ? ks - KH : 0], h2[ks >= KH ? ks - KH : 0]);
+      bf[ks] = live ? u : zero;
+    } else {
+      bf[ks] = raw[ks];
+      if (relu_in) bf[ks] = __builtin_elementwise_max(bf[ks], zero);
+    }
+  }
+}
+
+// Overlap-add of the 16 taps for the output quad (2j .. 2j+1, 2i .. 2i+1) of small-grid pixel (j, i):
+//   o[py * 2 + px] = sum_{ty,tx} col[(j+py-ty, i+px-tx)][(1-py+2ty)*4 + 1-px+2tx]
+// colrow(sy, sx) returns the 16 taps of the col row of pixel (sy, sx), 8-byte aligned. The ORDER of the additions is part of the contract
+// (the fused launch and the two-launch form give equal bits): neighbours dy = -1, 0, 1 outermost, then dx = -1, 0, 1, then py, then px,
+// every o[] starting from 0.f.
+// A tap is taken out of the aligned 8-byte word of its tap row (taps 4r .. 4r + 3): no 4-byte load at a 2-byte-aligned address.
+template <typename F>
+__device__ __forceinline__ f4_t c1_overlap_add(F&& colrow, int j, int i, int Hs, int Ws) {
+  float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int sy = j + dy, sx = i + dx;
+      if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) continue;
+      const uint64_t* rows = (const uint64_t*)colrow(sy, sx);
+#pragma unroll
+      for (int py = 0; py < 2; ++py)
+#pragma unroll
+        for (int px = 0; px < 2; ++px) {
+          const int ty = py - dy, tx = px - dx;
+          if (ty < 0 || ty > 1 || tx < 0 || tx > 1) continue;
+          const int tap = (1 - py + 2 * ty) * 4 + (1 - px + 2 * tx);
+          o[py * 2 + px] += (float)__builtin_bit_cast(half_t, (unsigned short)(rows[tap >> 2] >> (16 * (tap & 3))));
+        }
+    }
+  return f4_t{o[0], o[1], o[2], o[3]};
+}
+
+// the quad's two rows: post(o + b) [* out_scale when SCALED] as one float2 each at image row row0 + py, column 2i, to img and (the
+// caller's copy of the saved output) img2
+template <bool SCALED>
+__device__ __forceinline__ void c1_store_quad(f4_t o, float b, int post, float* img, float* img2, int64_t row0, int W, int i,
+                                              float out_scale = 1.f) {
+#pragma unroll
+  for (int py = 0; py < 2; ++py) {
+    float v0 = o[py * 2] + b, v1 = o[py * 2 + 1] + b;
+    if (post == 1) { v0 = tanhf(v0); v1 = tanhf(v1); }
+    const int64_t oo = (row0 + py) * W + 2 * i;
+    if constexpr (SCALED) {
+      *(float2*)(img + oo) = make_float2(v0 * out_scale, v1 * out_scale);
+      if (img2) *(float2*)(img2 + oo) = make_float2(v0 * out_scale, v1 * out_scale);
+    } else {
+      *(float2*)(img + oo) = make_float2(v0, v1);
+      if (img2) *(float2*)(img2 + oo) = make_float2(v0, v1);
+    }
+  }
+}
+
 // ---- fp16 transposed conv to one channel on the matrix cores -------------------------------------
 // col[p][tap] = sum_c relu?(X[p][c]) * w[c][tap]: D[tap][pixel] = A[tap][c] * B[c][pixel] with
 // v_mfma_f32_16x16x32_f16; B fragments are 16-byte row loads of X straight from global memory (each
@@ -274,71 +408,31 @@ __global__ void __launch_bounds__(256) c1_col_kernel(const char* X, const float*
                                                      int64_t P, int ldx, int coffx, int relu_in, const char* X2, int ld2,
                                                      const float* __restrict__ sc2, const float* __restrict__ sh2, BnAccP fa, int use_fa) {
   constexpr int KH = KS / 2;
-  __shared__ float aff[2][KH * 32];
+  __shared__ float aff[2 * KH * 32];
   const int lane = threadIdx.x & 63;
   const int tapr = lane & 15, kq = lane >> 4;
   const int64_t ngroups = (P + 15) / 16;
   const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * 256) >> 6;
-  const h8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
   // a wave walks 4+ groups: the next group's 16-byte row pieces are requested before this group's are used
   auto load_g = [&](int64_t g, h8_t (&raw)[KS]) {
     const int64_t pix = g * 16 + tapr;   // this lane's B column = pixel
-    const bool live = pix < P;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (X2 && ks >= KH) raw[ks] = live ? *(const h8_t*)(X2 + ((pix * ld2 + (ks - KH) * 32 + kq * 8) << 1)) : zero;
-      else raw[ks] = live ? *(const h8_t*)(X + ((pix * ldx + coffx + ks * 32 + kq * 8) << 1)) : zero;
-    }
+    for (int ks = 0; ks < KS; ++ks) raw[ks] = c1_col_load<KS>(X, X2, pix, pix < P, ldx, coffx, ld2, kq, ks);
   };
   h8_t raw[KS], nxt[KS];
   int64_t g = wave;
   if (g < ngroups) load_g(g, raw);
   h8_t af[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) af[ks][j] = (half_t)w[(ks * 32 + kq * 8 + j) * 16 + tapr];
+  c1_col_afrag<KS>(w, tapr, kq, af);
   float s2[KH][8], h2[KH][8];
-  if (X2) {
-    if (use_fa) {
-      if (threadIdx.x < KH * 32) {
-        float a, b;
-        bn_from_acc(fa, KH * 32, threadIdx.x, 0, blockIdx.x == 0, a, b);
-        aff[0][threadIdx.x] = a;
-        aff[1][threadIdx.x] = b;
-      }
-      if (blockIdx.x == 0 && fa.zero_next) zero_words64(fa.zero_next, fa.zero_words);
-      __syncthreads();
-#pragma unroll
-      for (int ks = 0; ks < KH; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s2[ks][j] = aff[0][ks * 32 + kq * 8 + j]; h2[ks][j] = aff[1][ks * 32 + kq * 8 + j]; }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < KH; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s2[ks][j] = sc2[ks * 32 + kq * 8 + j]; h2[ks][j] = sh2[ks * 32 + kq * 8 + j]; }
-    }
-  }
+  if (X2) c1_upper_coefs<KH>((lds_float_t*)aff, fa, use_fa, sc2, sh2, kq, s2, h2);
   for (; g < ngroups; g += nwaves) {
     if (g + nwaves < ngroups) load_g(g + nwaves, nxt);
     const int64_t pix = g * 16 + tapr;
     const bool live = pix < P;
     h8_t bf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (X2 && ks >= KH) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float t = fmaf((float)raw[ks][j], s2[ks >= KH ? ks - KH : 0][j], h2[ks >= KH ? ks - KH : 0][j]);
-          bf[ks][j] = live ? (half_t)(t > 0.f ? t : 0.f) : (half_t)0.f;
-        }
-      } else {
-        bf[ks] = raw[ks];
-        if (relu_in) bf[ks] = __builtin_elementwise_max(bf[ks], zero);
-      }
-    }
+    c1_col_bfrag<KS>(raw, X2 != nullptr, relu_in, live, s2, h2, bf);
     f4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks], bf[ks], acc, 0, 0, 0);
@@ -351,7 +445,7 @@ __global__ void __launch_bounds__(256) c1_col_kernel(const char* X, const float*
   }
 }
 
-// overlap-add of the 16 taps: out(2j+py, 2i+px) = post(bias + sum_{ty,tx} col[(j+py-ty, i+px-tx)][(1-py+2ty)*4 + 1-px+2tx])
+// overlap-add of the col tensor (c1_overlap_add), bias, tanh (post = 1), out_scale: one thread per small-grid pixel
 __global__ void __launch_bounds__(256) c1_col2im_kernel(const half_t* __restrict__ col, const float* __restrict__ bias,
                                                         float* img, float* img2, int n, int Hs, int Ws, int post, float out_scale) {
   const int64_t total = (int64_t)n * Hs * Ws;
@@ -362,42 +456,18 @@ __global__ void __launch_bounds__(256) c1_col2im_kernel(const half_t* __restrict
     const int64_t t = pix / Ws;
     const int j = (int)(t % Hs);
     const int nn = (int)(t / Hs);
-    float o[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int sy = j + dy, sx = i + dx;
-        if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) continue;
-        const half_t* cp = col + (((int64_t)nn * Hs + sy) * Ws + sx) * 16;
-        const h8_t c0 = *(const h8_t*)cp, c1 = *(const h8_t*)(cp + 8);
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-          for (int px = 0; px < 2; ++px) {
-            const int ty = py - dy, tx = px - dx;
-            if (ty < 0 || ty > 1 || tx < 0 || tx > 1) continue;
-            const int tap = (1 - py + 2 * ty) * 4 + (1 - px + 2 * tx);
-            o[py * 2 + px] += tap < 8 ? (float)c0[tap & 7] : (float)c1[tap & 7];
-          }
-      }
-#pragma unroll
-    for (int py = 0; py < 2; ++py) {
-      float v0 = o[py * 2] + b, v1 = o[py * 2 + 1] + b;
-      if (post == 1) { v0 = tanhf(v0); v1 = tanhf(v1); }
-      const int64_t oo = ((int64_t)nn * H + 2 * j + py) * W + 2 * i;
-      *(float2*)(img + oo) = make_float2(v0 * out_scale, v1 * out_scale);
-      if (img2) *(float2*)(img2 + oo) = make_float2(v0 * out_scale, v1 * out_scale);   // the caller's copy of the saved output
-    }
+    // (col rows are 32 bytes apart: 8-byte aligned, as c1_overlap_add needs)
+    const f4_t o = c1_overlap_add([=](int sy, int sx) { return col + (((int64_t)nn * Hs + sy) * Ws + sx) * 16; }, j, i, Hs, Ws);
+    c1_store_quad<true>(o, b, post, img, img2, (int64_t)nn * H + 2 * j, W, i, out_scale);
   }
 }
 
 // ---- the same two steps in ONE launch (round 4) ----------------------------------------------------------------------------
 // A workgroup owns TH rows of one image of the small grid (all Ws columns, so only rows have a halo): it computes col[p][tap] for
-// its TH + 2 rows on the MFMA exactly as c1_col_kernel does (same fragments, same fp16 rounding of col), keeps them in LDS
-// ((TH + 2) x Ws x 32 bytes) and overlap-adds its own TH rows with c1_col2im_kernel's loop order - bit-identical output, the col
-// tensor (16.8 MB written and re-read at the headline shape) and one launch gone; the price is (TH + 2) / TH of the input reads,
-// the extra rows being the neighbour workgroup's (L2). u1 of the generator at 256x256, n = 32: 28.6 + 15.6 us -> see DESIGN.md.
+// its TH + 2 rows on the MFMA with the pieces c1_col_kernel is made of, keeps them in LDS ((TH + 2) x Ws x 32 bytes) and overlap-adds its
+// own TH rows with c1_overlap_add, as c1_col2im_kernel does - bit-identical output, the col tensor (16.8 MB written and re-read at the
+// headline shape) and one launch gone; the price is (TH + 2) / TH of the input reads, the extra rows being the neighbour workgroup's
+// (L2). u1 of the generator at 256x256, n = 32: 28.6 + 15.6 us -> see DESIGN.md.
 template <int KS>   // KS = c / 32
 __global__ void __launch_bounds__(256) c1_scatter_fused_kernel(const char* X, const float* __restrict__ w, const float* __restrict__ bias,
                                                                float* img, float* img2, int Hs, int Ws, int TH, int ldx, int coffx, int relu_in,
@@ -412,66 +482,28 @@ __global__ void __launch_bounds__(256) c1_scatter_fused_kernel(const char* X, co
   const int bands = (Hs + TH - 1) / TH;
   const int nn = blockIdx.x / bands, y0 = (blockIdx.x % bands) * TH;
   const int gpr = Ws >> 4, G = (TH + 2) * gpr;                 // pixel groups of 16 along a row
-  const h8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  // the row pieces of the next TWO groups of a wave are in flight (c1_col_kernel: one)
   auto load_g = [&](int g, h8_t (&raw)[KS]) {
     const int ry = g / gpr, x = (g - ry * gpr) * 16 + tapr, y = y0 - 1 + ry;
     const bool live = g < G && y >= 0 && y < Hs;
     const int64_t pix = ((int64_t)nn * Hs + (live ? y : 0)) * Ws + x;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (X2 && ks >= KH) raw[ks] = live ? *(const h8_t*)(X2 + ((pix * ld2 + (ks - KH) * 32 + kq * 8) << 1)) : zero;
-      else raw[ks] = live ? *(const h8_t*)(X + ((pix * ldx + coffx + ks * 32 + kq * 8) << 1)) : zero;
-    }
+    for (int ks = 0; ks < KS; ++ks) raw[ks] = c1_col_load<KS>(X, X2, pix, live, ldx, coffx, ld2, kq, ks);
   };
   h8_t raw[KS], nx1[KS], nx2[KS];
   int g = wave;
   load_g(g, raw);
   load_g(g + 4, nx1);
   h8_t af[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) af[ks][j] = (half_t)w[(ks * 32 + kq * 8 + j) * 16 + tapr];
+  c1_col_afrag<KS>(w, tapr, kq, af);
   float s2[KH][8], h2[KH][8];
-  if (X2) {
-    if (use_fa) {
-      if (threadIdx.x < KH * 32) {
-        float a, b;
-        bn_from_acc(fa, KH * 32, threadIdx.x, 0, blockIdx.x == 0, a, b);
-        aff[threadIdx.x] = a;
-        aff[KH * 32 + threadIdx.x] = b;
-      }
-      if (blockIdx.x == 0 && fa.zero_next) zero_words64(fa.zero_next, fa.zero_words);
-      __syncthreads();
-#pragma unroll
-      for (int ks = 0; ks < KH; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s2[ks][j] = aff[ks * 32 + kq * 8 + j]; h2[ks][j] = aff[KH * 32 + ks * 32 + kq * 8 + j]; }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < KH; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s2[ks][j] = sc2[ks * 32 + kq * 8 + j]; h2[ks][j] = sh2[ks * 32 + kq * 8 + j]; }
-    }
-  }
+  if (X2) c1_upper_coefs<KH>((lds_float_t*)aff, fa, use_fa, sc2, sh2, kq, s2, h2);
   for (; g < G; g += 4) {
     load_g(g + 8, nx2);
     const int ry = g / gpr, x = (g - ry * gpr) * 16 + tapr, y = y0 - 1 + ry;
     const bool live = y >= 0 && y < Hs;
     h8_t bf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (X2 && ks >= KH) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float t = fmaf((float)raw[ks][j], s2[ks >= KH ? ks - KH : 0][j], h2[ks >= KH ? ks - KH : 0][j]);
-          bf[ks][j] = live ? (half_t)(t > 0.f ? t : 0.f) : (half_t)0.f;
-        }
-      } else {
-        bf[ks] = raw[ks];
-        if (relu_in) bf[ks] = __builtin_elementwise_max(bf[ks], zero);
-      }
-    }
+    c1_col_bfrag<KS>(raw, X2 != nullptr, relu_in, live, s2, h2, bf);
     f4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[ks], bf[ks], acc, 0, 0, 0);
@@ -481,39 +513,14 @@ __global__ void __launch_bounds__(256) c1_scatter_fused_kernel(const char* X, co
     for (int ks = 0; ks < KS; ++ks) { raw[ks] = nx1[ks]; nx1[ks] = nx2[ks]; }
   }
   __syncthreads();
-  // overlap-add (c1_col2im_kernel's order of additions): out(2j+py, 2i+px) = post(bias + sum col[(j+py-ty, i+px-tx)][tap])
   const int H = 2 * Hs, W = 2 * Ws;
   const float b = bias ? bias[0] : 0.f;
   for (int p = threadIdx.x; p < TH * Ws; p += 256) {
     const int jl = p / Ws, i = p - jl * Ws, j = y0 + jl;
     if (j >= Hs) break;
-    float o[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int sy = j + dy, sx = i + dx;
-        if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) continue;
-        const half_t* cp = col + ((int64_t)(jl + 1 + dy) * Ws + sx) * 16;
-        const h8_t c0 = *(const h8_t*)cp, c1 = *(const h8_t*)(cp + 8);
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-          for (int px = 0; px < 2; ++px) {
-            const int ty = py - dy, tx = px - dx;
-            if (ty < 0 || ty > 1 || tx < 0 || tx > 1) continue;
-            const int tap = (1 - py + 2 * ty) * 4 + (1 - px + 2 * tx);
-            o[py * 2 + px] += tap < 8 ? (float)c0[tap & 7] : (float)c1[tap & 7];
-          }
-      }
-#pragma unroll
-    for (int py = 0; py < 2; ++py) {
-      float v0 = o[py * 2] + b, v1 = o[py * 2 + 1] + b;
-      if (post == 1) { v0 = tanhf(v0); v1 = tanhf(v1); }
-      const int64_t oo = ((int64_t)nn * H + 2 * j + py) * W + 2 * i;
-      *(float2*)(img + oo) = make_float2(v0 * out_scale, v1 * out_scale);
-      if (img2) *(float2*)(img2 + oo) = make_float2(v0 * out_scale, v1 * out_scale);
-    }
+    // band row 0 = y0 - 1; rows of 32 bytes in 16-byte aligned LDS: 8-byte aligned, as c1_overlap_add needs
+    const f4_t o = c1_overlap_add([=](int sy, int sx) { return col + ((int64_t)(sy - y0 + 1) * Ws + sx) * 16; }, j, i, Hs, Ws);
+    c1_store_quad<true>(o, b, post, img, img2, (int64_t)nn * H + 2 * j, W, i, out_scale);
   }
 }
 
@@ -572,34 +579,10 @@ __global__ void __launch_bounds__(256) c1_col2im_mc_kernel(const half_t* __restr
     const int64_t t = pix / Ws;
     const int j = (int)(t % Hs);
     const int nn = (int)(t / Hs);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int sy = j + dy, sx = i + dx;
-        if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) continue;
-        const half_t* cp = col + ((((int64_t)nn * Hs + sy) * Ws + sx) * OC + o) * 16;
-        const h8_t c0 = *(const h8_t*)cp, c1 = *(const h8_t*)(cp + 8);
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-          for (int px = 0; px < 2; ++px) {
-            const int ty = py - dy, tx = px - dx;
-            if (ty < 0 || ty > 1 || tx < 0 || tx > 1) continue;
-            const int tap = (1 - py + 2 * ty) * 4 + (1 - px + 2 * tx);
-            acc[py * 2 + px] += tap < 8 ? (float)c0[tap & 7] : (float)c1[tap & 7];
-          }
-      }
+    static_assert((16 * sizeof(half_t)) % 8 == 0, "c1_overlap_add reads 8-byte words of a channel's col row");
+    const f4_t acc = c1_overlap_add([=](int sy, int sx) { return col + ((((int64_t)nn * Hs + sy) * Ws + sx) * OC + o) * 16; }, j, i, Hs, Ws);
     const float b = bias ? bias[o] : 0.f;
-#pragma unroll
-    for (int py = 0; py < 2; ++py) {
-      float v0 = acc[py * 2] + b, v1 = acc[py * 2 + 1] + b;
-      if (post == 1) { v0 = tanhf(v0); v1 = tanhf(v1); }
-      const int64_t oo = (((int64_t)nn * OC + o) * H + 2 * j + py) * W + 2 * i;
-      *(float2*)(img + oo) = make_float2(v0, v1);
-      if (img2) *(float2*)(img2 + oo) = make_float2(v0, v1);
-    }
+    c1_store_quad<false>(acc, b, post, img, img2, ((int64_t)nn * OC + o) * H + 2 * j, W, i);   // (no out_scale here: stored unscaled)
   }
 }
 
@@ -903,14 +886,7 @@ __global__ void __launch_bounds__(256) c1_wgrad_mfma_kernel(const char* X, const
     for (int i = 0; i < NP; ++i) {
       u4_t v = xv[i];
       if (upper) {
-        const h8_t raw = __builtin_bit_cast(h8_t, v);
-        h8_t o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float tt = fmaf((float)raw[j], s2[j], h2[j]);
-          o[j] = (half_t)(tt > 0.f ? tt : 0.f);
-        }
-        v = __builtin_bit_cast(u4_t, o);
+        v = __builtin_bit_cast(u4_t, c1_upper8(__builtin_bit_cast(h8_t, v), s2, h2));
       } else if (relu_in) {
         typedef short s8_t __attribute__((ext_vector_type(8)));
         s8_t hh = __builtin_bit_cast(s8_t, v);
@@ -983,570 +959,30 @@ __global__ void __launch_bounds__(256) c1_wgrad_reduce_kernel(const float* __res
   }
 }
 
-// ---- discriminator head ----------------------------------------------------------------------
-// h[n,py,px] = sum_{ky,kx,c} a4[n,py+ky,px+kx,c] * w5[ky*4+kx][c]     (Conv2d(512,1,4,1,0), networks.py:352)
-template <typename T>
-__global__ void __launch_bounds__(256) head_conv_kernel(const char* a4, const float* __restrict__ w5, float* h, int Hh,
-                                                        int Wh, int c) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  __shared__ float red[4];
-  const int Ph = Hh - 3, Pw = Wh - 3;
-  const int o = blockIdx.x;  // (n, py, px)
-  const int px = o % Pw, py = (o / Pw) % Ph, nn = o / (Pw * Ph);
-  const int cpt = c / EPC;  // chunks per tap
-  float s = 0.f;
-  for (int idx = threadIdx.x; idx < 16 * cpt; idx += 256) {
-    const int tap = idx / cpt, cc = idx % cpt;
-    const int iy = py + (tap >> 2), ix = px + (tap & 3);
-    const char* src = a4 + ((((int64_t)nn * Hh + iy) * Wh + ix) * c + cc * EPC) * (int64_t)sizeof(T);
-    const float* wr = w5 + tap * c + cc * EPC;
-    if constexpr (std::is_same<T, half_t>::value) {
-      const h8_t v = *(const h8_t*)src;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) s = fmaf((float)v[e], wr[e], s);
-    } else {
-      const f4_t v = *(const f4_t*)src;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) s = fmaf(v[e], wr[e], s);
-    }
+// C1Affine as the kernels take it (all null / 0 without one)
+struct C1AffineP { const char* x2; int ld2; const float* sc2; const float* sh2; BnAccP fa; int use_fa; };
+C1AffineP c1_affine_p(const C1Affine* aff) {
+  C1AffineP p = {};
+  if (aff) {
+    p.x2 = (const char*)aff->x2; p.ld2 = aff->ld2; p.sc2 = aff->scale; p.sh2 = aff->shift;
+    if (aff->bn) { p.use_fa = 1; gi_fill_acc_params(p.fa, *aff->bn); }
   }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) h[o] = red[0] + red[1] + red[2] + red[3];
-}
-
-// out[n] = [sigmoid](bl + sum_p wl[p]*h[n,p])     (Flatten + Linear(P,1) [+ Sigmoid], networks.py:353-357)
-__global__ void __launch_bounds__(64) head_linear_kernel(const float* h, const float* wl, const float* bl, float* out,
-                                                         int P, int sigmoid) {
-  const int nn = blockIdx.x;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < P; i += 64) s = fmaf(h[(int64_t)nn * P + i], wl[i], s);
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if (threadIdx.x == 0) {
-    s += bl[0];
-    out[nn] = sigmoid ? 1.f / (1.f + expf(-s)) : s;
-  }
-}
-
-// dz[n] = dy[n] * (sigmoid ? out(1-out) : 1); dh[n,p] = dz[n]*wl[p]; dwl[p] += sum_n dz[n]*h[n,p]; dbl += sum dz
-__global__ void __launch_bounds__(256) head_linear_bwd_kernel(const float* dy, const float* out, const float* h,
-                                                              const float* wl, float* dh, float* dwl, float* dbl, int n,
-                                                              int P, int sigmoid) {
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < P; p += gridDim.x * 256) {
-    float gw = 0.f;
-    for (int nn = 0; nn < n; ++nn) {
-      const float o = out[nn];
-      const float dz = dy[nn] * (sigmoid ? o * (1.f - o) : 1.f);
-      dh[(int64_t)nn * P + p] = dz * wl[p];
-      gw = fmaf(dz, h[(int64_t)nn * P + p], gw);
-    }
-    if (dwl) atomicAdd(dwl + p, gw);
-  }
-  if (dbl && blockIdx.x == 0 && threadIdx.x == 0) {
-    float gb = 0.f;
-    for (int nn = 0; nn < n; ++nn) {
-      const float o = out[nn];
-      gb += dy[nn] * (sigmoid ? o * (1.f - o) : 1.f);
-    }
-    atomicAdd(dbl, gb);
-  }
-}
-
-// da4[n,y,x,c] = loss_scale * sum_{tap: (y-ky,x-kx) valid} dh[n,y-ky,x-kx] * w5[tap][c]
-template <typename T>
-__global__ void __launch_bounds__(256) head_dgrad_kernel(const float* dh, const float* __restrict__ w5, char* da4, int n,
-                                                         int Hh, int Wh, int c, float loss_scale) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int Ph = Hh - 3, Pw = Wh - 3;
-  const int cpt = c / EPC;
-  const int64_t total = (int64_t)n * Hh * Wh * cpt;
-  for (int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (int64_t)gridDim.x * 256) {
-    const int cc = (int)(gid % cpt);
-    const int64_t pix = gid / cpt;
-    const int x = (int)(pix % Wh), y = (int)((pix / Wh) % Hh), nn = (int)(pix / ((int64_t)Wh * Hh));
-    float s[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) s[e] = 0.f;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) {
-      const int py = y - (tap >> 2), px = x - (tap & 3);
-      if (py < 0 || py >= Ph || px < 0 || px >= Pw) continue;
-      const float g = dh[((int64_t)nn * Ph + py) * Pw + px];
-      const float* wr = w5 + tap * c + cc * EPC;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) s[e] = fmaf(g, wr[e], s[e]);
-    }
-    T* dst = (T*)(da4 + (pix * c + cc * EPC) * (int64_t)sizeof(T));
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) dst[e] = (T)(s[e] * loss_scale);
-  }
-}
-
-// dw5[tap][c] += sum_{n,p} dh[n,p] * a4[n,p+tap][c]   (grid.y = n, grid.z = output row py)
-// part != null: the (image, row band) blocks store their sums there ([block][16 c]) and head_wgrad_sum_kernel adds them in block
-// order - bit-reproducible (the fp32 critic of BASELINE config 2); part == null: float atomics into dw5
-template <typename T>
-__global__ void __launch_bounds__(256) head_wgrad_kernel(const float* dh, const char* a4, float* dw5, int Hh, int Wh,
-                                                         int c, float* part) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int Ph = Hh - 3, Pw = Wh - 3;
-  const int cpt = c / EPC;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= 16 * cpt) return;
-  const int tap = idx / cpt, cc = idx % cpt;
-  // blockIdx.z covers a band of output rows: 1/band of the atomics (they contend on 16*c addresses)
-  const int nn = blockIdx.y;
-  const int band = (Ph + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int py0 = blockIdx.z * band, py1 = min(Ph, py0 + band);
-  float s[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) s[e] = 0.f;
-  for (int py = py0; py < py1; ++py)
-  for (int px = 0; px < Pw; ++px) {
-    const float g = dh[((int64_t)nn * Ph + py) * Pw + px];
-    const char* src = a4 + ((((int64_t)nn * Hh + py + (tap >> 2)) * Wh + px + (tap & 3)) * c + cc * EPC) * (int64_t)sizeof(T);
-    if constexpr (std::is_same<T, half_t>::value) {
-      const h8_t v = *(const h8_t*)src;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) s[e] = fmaf(g, (float)v[e], s[e]);
-    } else {
-      const f4_t v = *(const f4_t*)src;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) s[e] = fmaf(g, v[e], s[e]);
-    }
-  }
-  if (part) {
-    float* o = part + ((int64_t)blockIdx.y * gridDim.z + blockIdx.z) * 16 * c + tap * c + cc * EPC;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) o[e] = s[e];
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) atomicAdd(dw5 + tap * c + cc * EPC + e, s[e]);
-}
-__global__ void __launch_bounds__(256) head_wgrad_sum_kernel(const float* part, int nparts, float* dw5, int count) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= count) return;
-  float s = 0.f;
-  for (int k = 0; k < nparts; ++k) s += part[(int64_t)k * count + i];
-  dw5[i] += s;
-}
-
-// ---- fp16 head at c = 512 (the PatchGAN of networks.py:331-363): one pixel row = 1 KiB = one wave load --------
-// Forward, one workgroup per image: t[px][tap] = a4[px][:] . w5[tap][:] on the MFMA (16 px x 16 taps x 32 channels
-// per instruction; w5 as fp16 fragments resident in registers, fp32 accumulation), so every activation is read once;
-// then h[p] = sum_tap t[p + (ky,kx)][tap], the Linear(P,1) and the optional sigmoid in the same workgroup.
-constexpr int HT_PITCH = 17;   // floats per pixel row of t in LDS (16 taps + 1: conflict-free column reads)
-__global__ void __launch_bounds__(1024) head_fwd512_kernel(const char* __restrict__ a4, const float* __restrict__ w5,
-                                                           const float* __restrict__ wl, const float* __restrict__ bl,
-                                                           float* __restrict__ h, float* __restrict__ out,
-                                                           float* __restrict__ out2, int Hh, int Wh, int sigmoid,
-                                                           const float* __restrict__ sc4, const float* __restrict__ sh4,
-                                                           int n_per_group, int gstride, float* __restrict__ tbuf, int slices,
-                                                           BnAccP fa, int use_fa) {
-  // tbuf != null (large feature maps, few images): `slices` workgroups per image each compute t for their share of
-  // the pixel tiles into tbuf[image][pixel][16] and stop; head_h512_kernel finishes (h, Linear, sigmoid).
-  // sc4 != null: a4 is the RAW conv4 output; LeakyReLU(fma(x, sc4, sh4)) (the layer's BatchNorm + activation, the
-  // population of image nn at +gstride floats) is applied to the fragments as they are loaded, the same fp32
-  // expression and fp16 rounding as the separate apply pass
-  extern __shared__ float t_lds[];   // [Hh*Wh][HT_PITCH] | 16 partial sums | w5 as fp16 [16 taps][512] | scale, shift [2][512]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nn = tbuf ? blockIdx.x / slices : blockIdx.x, npx = Hh * Wh;
-  float* red = t_lds + (tbuf ? 0 : ((npx * HT_PITCH + 3) & ~3));   // 16-byte aligned
-  half_t* wh = (half_t*)(red + 16);
-  float* aff = (float*)(wh + 16 * 512);
-  // this wave's first pixel tile is requested before the prologue (weights to LDS, the scale / shift derivation with its accumulator
-  // round trip): at the critic's map sizes a wave owns ONE tile, so that is all of its activation traffic
-  const char* img = a4 + (int64_t)nn * npx * 1024;
-  const int ntile = (npx + 15) / 16;
-  const int tile0 = tbuf ? (int)((int64_t)ntile * (blockIdx.x % slices) / slices) : 0;
-  const int tile1 = tbuf ? (int)((int64_t)ntile * (blockIdx.x % slices + 1) / slices) : ntile;
-  h8_t av[16];
-  constexpr int AV_EARLY = 12;   // chunks requested before the prologue; the rest behind it (all 16 + the prologue's 64 accumulator
-                                 // registers went 16 bytes over the 128 VGPRs of a 1024-thread workgroup)
-  const char* row0;
-  {
-    const int t0 = tile0 + wave < tile1 ? tile0 + wave : tile0;     // (a wave without a tile loads one it will not use)
-    row0 = img + (int64_t)min(t0 * 16 + (lane & 15), npx - 1) * 1024 + (lane >> 4) * 16;
-#pragma unroll
-    for (int ks = 0; ks < AV_EARLY; ++ks) av[ks] = *(const h8_t*)(row0 + ks * 64);
-  }
-  if (sc4 && use_fa) {
-    // the scale / shift vectors do not exist yet: derived here from conv4's exact accumulators (bn_acc.h) - every workgroup the
-    // vectors of its image's population; workgroup 0 publishes ALL populations' vectors (sc4 / sh4 and the backward's), moves the
-    // running statistics population by population and clears the layer's other accumulator region: no finalize launch
-    const int grp = nn / n_per_group;
-    if (threadIdx.x < 512) {
-      float a = 0.f, b = 0.f;
-      if (blockIdx.x == 0) {
-        for (int j = 0; j < fa.groups; ++j) {
-          float aj, bj;
-          bn_from_acc(fa, 512, threadIdx.x, j, true, aj, bj);
-          if (j == grp) { a = aj; b = bj; }
-        }
-      } else {
-        bn_from_acc(fa, 512, threadIdx.x, grp, false, a, b);
-      }
-      aff[threadIdx.x] = a;
-      aff[512 + threadIdx.x] = b;
-    }
-    if (blockIdx.x == 0 && fa.zero_next) {
-      for (int i = threadIdx.x; i < fa.zero_words; i += 1024) fa.zero_next[i] = 0ull;
-    }
-  } else if (sc4) {
-    const int go = (nn / n_per_group) * gstride;
-    for (int i = threadIdx.x; i < 512; i += 1024) { aff[i] = sc4[go + i]; aff[512 + i] = sh4[go + i]; }
-  }
-  for (int i = threadIdx.x; i < 16 * 512 / 4; i += 1024) {
-    const f4_t v = *(const f4_t*)(w5 + i * 4);
-    *(h4_t*)(wh + i * 4) = h4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-  }
-#pragma unroll
-  for (int ks = AV_EARLY; ks < 16; ++ks) av[ks] = *(const h8_t*)(row0 + ks * 64);
-  __syncthreads();
-  // (the weight fragments are read from LDS next to their MFMA: kept in registers beside av - 64 + 64 of the 128 a 1024-thread
-  //  workgroup has per lane - the kernel spilled 132 bytes per lane, and at the critic's map sizes a wave owns one tile anyway)
-  const half_t* bfp = wh + (lane & 15) * 512 + (lane >> 4) * 8;
-  for (int tile = tile0 + wave; tile < tile1; tile += 16) {
-    if (tile != tile0 + wave) {      // later tiles of this wave (large maps)
-      const int px = min(tile * 16 + (lane & 15), npx - 1);
-      const char* row = img + (int64_t)px * 1024 + (lane >> 4) * 16;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) av[ks] = *(const h8_t*)(row + ks * 64);
-    }
-    if (sc4) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        const float* a0 = aff + ks * 32 + (lane >> 4) * 8;
-        const f4_t s0 = *(const f4_t*)a0, s1 = *(const f4_t*)(a0 + 4), h0 = *(const f4_t*)(a0 + 512), h1 = *(const f4_t*)(a0 + 516);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float t = fmaf((float)av[ks][j], j < 4 ? s0[j & 3] : s1[j & 3], j < 4 ? h0[j & 3] : h1[j & 3]);
-          av[ks][j] = (half_t)(t > 0.f ? t : 0.2f * t);
-        }
-      }
-    }
-    f4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[ks], *(const h8_t*)(bfp + ks * 32), acc, 0, 0, 0);
-    // D[row = pixel][col = tap]: lane holds tap (lane&15), pixels 4*(lane>>4) + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = tile * 16 + 4 * (lane >> 4) + r;
-      if (q < npx) {
-        if (tbuf) tbuf[((int64_t)nn * npx + q) * 16 + (lane & 15)] = acc[r];
-        else t_lds[q * HT_PITCH + (lane & 15)] = acc[r];
-      }
-    }
-  }
-  if (tbuf) return;
-  __syncthreads();
-  const int Ph = Hh - 3, Pw = Wh - 3, P = Ph * Pw;
-  float part = 0.f;
-  for (int p = threadIdx.x; p < P; p += 1024) {
-    const int py = p / Pw, px = p - py * Pw;
-    float sacc = 0.f;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) sacc += t_lds[((py + (tap >> 2)) * Wh + px + (tap & 3)) * HT_PITCH + tap];
-    h[(int64_t)nn * P + p] = sacc;
-    part = fmaf(sacc, wl[p], part);
-  }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  if (lane == 0) red[wave] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float z = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) z += red[w];
-    z += bl[0];
-    z = sigmoid ? 1.f / (1.f + expf(-z)) : z;
-    out[nn] = z;
-    if (out2) out2[nn] = z;
-  }
-}
-
-// second stage of the sliced forward: h[p] = sum_tap t[p + (ky,kx)][tap], Linear(P,1), sigmoid; one workgroup per image
-__global__ void __launch_bounds__(256) head_h512_kernel(const float* __restrict__ tbuf, const float* __restrict__ wl,
-                                                        const float* __restrict__ bl, float* __restrict__ h,
-                                                        float* __restrict__ out, float* __restrict__ out2, int Hh, int Wh,
-                                                        int sigmoid) {
-  __shared__ float red[4];
-  const int nn = blockIdx.x, npx = Hh * Wh, Ph = Hh - 3, Pw = Wh - 3, P = Ph * Pw;
-  const float* t = tbuf + (int64_t)nn * npx * 16;
-  float part = 0.f;
-  for (int p = threadIdx.x; p < P; p += 256) {
-    const int py = p / Pw, px = p - py * Pw;
-    float sacc = 0.f;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) sacc += t[((py + (tap >> 2)) * Wh + px + (tap & 3)) * 16 + tap];
-    h[(int64_t)nn * P + p] = sacc;
-    part = fmaf(sacc, wl[p], part);
-  }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float z = ((red[0] + red[1]) + (red[2] + red[3])) + bl[0];
-    z = sigmoid ? 1.f / (1.f + expf(-z)) : z;
-    out[nn] = z;
-    if (out2) out2[nn] = z;
-  }
-}
-
-// Backward, two roles by blockIdx in one launch (dh[n,p] = dz[n]*wl[p] is never materialised):
-//   [0, nb)        input gradient: da4[n,y,x,:] = loss_scale * sum_tap dh[n,y-ky,x-kx] * w5[tap][:], a lane owns 8
-//                  channels with its 16x8 weights in registers, a wave owns a pixel (one 1-KiB store);
-//   [nb, 2nb)      weight-gradient partial of the same pixel range: acc[tap][8ch] += dh[..] * a4[n,y,x,8ch], reduced over
-//                  the 4 waves in LDS and stored to part[block][16][512] (summed in fixed order by head_wsum512_kernel);
-//   The Linear's gradients dwl[p] += sum_n dz[n]*h[n,p], dbl += sum_n dz[n] ride in head_wsum512_kernel.
-// Without parameter gradients (frozen critic) only the first nb blocks are launched.
-__global__ void __launch_bounds__(256) head_bwd512_kernel(const float* __restrict__ dy, const float* __restrict__ outv,
-                                                          const float* __restrict__ hsave, const float* __restrict__ wl,
-                                                          const float* __restrict__ w5, const char* __restrict__ a4,
-                                                          char* __restrict__ da4, float* __restrict__ part,
-                                                          float* __restrict__ dwl, float* __restrict__ dbl, int n, int Hh,
-                                                          int Wh, int bands, int sigmoid, float loss_scale,
-                                                          const float* __restrict__ sc4, const float* __restrict__ sh4,
-                                                          int n_per_group, int gstride, HeadBwdFuse hf) {
-  __shared__ float red[2 * 16 * 512];   // 64 KiB: two waves' accumulators at a time
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int Ph = Hh - 3, Pw = Wh - 3, P = Ph * Pw, npx = Hh * Wh;
-  const int nb = n * bands;
-  int b = blockIdx.x;
-  const bool wgrad = b >= nb;
-  if (wgrad) b -= nb;
-  const int nn = b / bands, band = b - nn * bands;
-  const int ppb = (npx + bands - 1) / bands;               // pixels per block
-  const int q0 = band * ppb, q1 = min(npx, q0 + ppb);
-  const float o = outv[nn];
-  const float dz = dy[nn] * (sigmoid ? o * (1.f - o) : 1.f) * (wgrad ? 1.f : loss_scale);
-  // gp[(py+3)*GW + px+3] = dz * wl[py*Pw+px] with a 3-wide zero border: dh of this image without bounds checks
-  const int GW = Pw + 6;
-  float* gp = red;
-  for (int i = threadIdx.x; i < (Ph + 6) * GW; i += 256) {
-    const int py = i / GW - 3, px = i - (py + 3) * GW - 3;
-    gp[i] = (py >= 0 && py < Ph && px >= 0 && px < Pw) ? dz * wl[py * Pw + px] : 0.f;
-  }
-  __syncthreads();
-  if (!wgrad) {
-    float w[16][8];
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) {
-      const f4_t lo = *(const f4_t*)(w5 + tap * 512 + lane * 8), hi = *(const f4_t*)(w5 + tap * 512 + lane * 8 + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { w[tap][e] = lo[e]; w[tap][4 + e] = hi[e]; }
-    }
-    // hf.acc != null: the BatchNorm-backward sums of the layer in front (HeadBwdArgs::bwd_*) from the gradient this block produces -
-    // the rounded value it stores, as the separate reduction would read it back - and the layer's raw output x, four pixels' rows
-    // of x requested ahead per wave
-    const bool bw = hf.acc != nullptr;
-    float bsc[8], bsh[8], bmu[8], biv[8], bs[8], bsx[8];
-    if (bw) {
-      const int go = (nn / hf.n_per_group) * hf.stride + lane * 8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { bsc[e] = hf.scale[go + e]; bsh[e] = hf.shift[go + e]; bmu[e] = hf.mean[go + e]; biv[e] = hf.inv[go + e]; bs[e] = bsx[e] = 0.f; }
-    }
-    const char* xrow = hf.x + (int64_t)nn * npx * 1024 + lane * 16;
-    for (int qb = q0 + wave; qb < q1; qb += 16) {
-      h8_t xs[4];
-      if (bw) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xs[j] = *(const h8_t*)(xrow + (int64_t)min(qb + 4 * j, npx - 1) * 1024);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int q = qb + 4 * j;
-        if (q < q1) {                              // wave-uniform
-          const int y = q / Wh, x = q - y * Wh;
-          const float* gq = gp + (y + 3) * GW + x + 3;
-          float g[16];
-#pragma unroll
-          for (int tap = 0; tap < 16; ++tap) g[tap] = gq[-(tap >> 2) * GW - (tap & 3)];   // LDS broadcast reads
-          float sacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int tap = 0; tap < 16; ++tap)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sacc[e] = fmaf(g[tap], w[tap][e], sacc[e]);
-          h8_t v;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (half_t)sacc[e];
-          *(h8_t*)(da4 + ((int64_t)nn * npx + q) * 1024 + lane * 16) = v;
-          if (bw) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float xf = (float)xs[j][e];
-              const float dz = (float)v[e] * (fmaf(xf, bsc[e], bsh[e]) > 0.f ? 1.f : hf.slope);
-              bs[e] += dz;
-              bsx[e] = fmaf(dz, (xf - bmu[e]) * biv[e], bsx[e]);
-            }
-          }
-        }
-      }
-    }
-    if (bw) {     // the four waves' sums through LDS (gp is done with), then one exact add per channel and quantity
-      __syncthreads();
-      float* fold = red;   // [4 waves][512][2]
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { fold[(wave * 512 + lane * 8 + e) * 2] = bs[e]; fold[(wave * 512 + lane * 8 + e) * 2 + 1] = bsx[e]; }
-      __syncthreads();
-      const int grp = nn / hf.n_per_group, rep = b & (hf.reps - 1);
-      for (int ch = threadIdx.x; ch < 512; ch += 256) {
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) { s0 += fold[(wv * 512 + ch) * 2]; s1 += fold[(wv * 512 + ch) * 2 + 1]; }
-        gi_stat_add(hf.acc, 512, rep, grp, 0, ch, s0);
-        gi_stat_add(hf.acc, 512, rep, grp, 1, ch, s1);
-      }
-    }
-    return;
-  }
-  float acc[16][8];
-#pragma unroll
-  for (int tap = 0; tap < 16; ++tap)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[tap][e] = 0.f;
-  float s4[8], h4[8];   // sc4 != null: a4 is the raw conv4 output (see head_fwd512_kernel); a lane owns 8 channels
-  if (sc4) {
-    const int go = (nn / n_per_group) * gstride + lane * 8;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s4[e] = sc4[go + e]; h4[e] = sh4[go + e]; }
-  }
-  const char* arow = a4 + (int64_t)nn * npx * 1024 + lane * 16;
-  for (int qb = q0 + wave; qb < q1; qb += 32) {   // 8 pixel rows in flight per wave
-    h8_t v[8];
-#pragma unroll
-    for (int jx = 0; jx < 8; ++jx) v[jx] = *(const h8_t*)(arow + (int64_t)min(qb + 4 * jx, npx - 1) * 1024);
-#pragma unroll
-    for (int jx = 0; jx < 8; ++jx) {
-      const int q = qb + 4 * jx;
-      if (q >= q1) break;                          // wave-uniform
-      const int y = q / Wh, x = q - y * Wh;
-      const float* gq = gp + (y + 3) * GW + x + 3;
-      float g[16];
-#pragma unroll
-      for (int tap = 0; tap < 16; ++tap) g[tap] = gq[-(tap >> 2) * GW - (tap & 3)];
-      float vf[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vf[e] = (float)v[jx][e];
-      if (sc4) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float t = fmaf(vf[e], s4[e], h4[e]);
-          vf[e] = (float)(half_t)(t > 0.f ? t : 0.2f * t);
-        }
-      }
-#pragma unroll
-      for (int tap = 0; tap < 16; ++tap)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[tap][e] = fmaf(g[tap], vf[e], acc[tap][e]);
-    }
-  }
-  __syncthreads();   // every wave is done with gp before red is reused
-  // waves 2,3 -> LDS, waves 0,1 add; wave 1 -> LDS, wave 0 adds and stores the block's partial
-  auto put = [&](int slot) {
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) {
-      float* d = red + slot * 8192 + tap * 512 + lane * 8;
-      *(f4_t*)d = f4_t{acc[tap][0], acc[tap][1], acc[tap][2], acc[tap][3]};
-      *(f4_t*)(d + 4) = f4_t{acc[tap][4], acc[tap][5], acc[tap][6], acc[tap][7]};
-    }
-  };
-  auto take = [&](int slot) {
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) {
-      const float* d = red + slot * 8192 + tap * 512 + lane * 8;
-      const f4_t lo = *(const f4_t*)d, hi = *(const f4_t*)(d + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { acc[tap][e] += lo[e]; acc[tap][4 + e] += hi[e]; }
-    }
-  };
-  if (wave >= 2) put(wave - 2);
-  __syncthreads();
-  if (wave < 2) take(wave);
-  __syncthreads();
-  if (wave == 1) put(0);
-  __syncthreads();
-  if (wave == 0) {
-    take(0);
-    float* dst = part + (int64_t)b * 8192;
-#pragma unroll
-    for (int tap = 0; tap < 16; ++tap) {
-      *(f4_t*)(dst + tap * 512 + lane * 8) = f4_t{acc[tap][0], acc[tap][1], acc[tap][2], acc[tap][3]};
-      *(f4_t*)(dst + tap * 512 + lane * 8 + 4) = f4_t{acc[tap][4], acc[tap][5], acc[tap][6], acc[tap][7]};
-    }
-  }
-}
-
-// dw5[i] += sum_b part[b][i] in a fixed order (deterministic): a workgroup owns 32 elements, 8 thread groups
-// each sum every 8th partial, LDS combines the groups. Workgroups 256 .. 256+P-1 compute dwl[p] (threads over the
-// batch, tree reduction), workgroup 256+P the Linear's bias gradient.
-__global__ void __launch_bounds__(256) head_wsum512_kernel(const float* __restrict__ part, int nb, float* __restrict__ dw5,
-                                                           const float* __restrict__ dy, const float* __restrict__ outv,
-                                                           const float* __restrict__ hsave, float* __restrict__ dwl,
-                                                           float* __restrict__ dbl, int n, int P, int sigmoid) {
-  __shared__ float red[8][32];
-  if (blockIdx.x >= 256) {
-    const int p = blockIdx.x - 256;
-    if (p == P && !dbl) return;
-    float g = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const float o = outv[i];
-      const float dz = dy[i] * (sigmoid ? o * (1.f - o) : 1.f);
-      g += p < P ? dz * hsave[(int64_t)i * P + p] : dz;
-    }
-    for (int off = 32; off > 0; off >>= 1) g += __shfl_xor(g, off);
-    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = g;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float t = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-      if (p < P) dwl[p] += t; else dbl[0] += t;
-    }
-    return;
-  }
-  const int e = threadIdx.x & 31, gq = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + e;   // < 8192
-  float s0 = 0.f, s1 = 0.f;
-  int b = gq;
-  for (; b + 8 < nb; b += 16) {
-    s0 += part[(int64_t)b * 8192 + i];
-    s1 += part[(int64_t)(b + 8) * 8192 + i];
-  }
-  if (b < nb) s0 += part[(int64_t)b * 8192 + i];
-  red[gq][e] = s0 + s1;
-  __syncthreads();
-  if (gq == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t += red[q][e];
-    dw5[i] += t;
-  }
-}
-
-// row bands per image for the backward: ~256 workgroups, at least 32 pixels each
-static bool head_fast() { return gi_opt(GI_OPT_HEAD_FAST) != 0; }   // GI_HEAD_FAST=0: the generic kernels
-static int head_bands(int n, int npx) {
-  int bands = 1;
-  while (n * bands < 256 && npx / (bands * 2) >= 32) bands *= 2;
-  return bands;
-}
-
-int grid_for(int64_t work_items, int per_block, int cap) {
-  int64_t b = (work_items + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
+  return p;
 }
 
 }  // namespace
 
-bool op_head_affine_ok(int dtype, int c) { return dtype == GI_F16 && c == 512 && head_fast(); }
-
-int64_t op_head_scratch_bytes(int max_n, int Hh, int Wh) {
-  (void)Hh; (void)Wh;   // n * head_bands(n, .) < 512 while bands > 1, = n otherwise
-  return (int64_t)(max_n > 512 ? max_n : 512) * 8192 * 4;
-}
+// 256-thread launch of KERNEL<half_t> or KERNEL<float> by `dtype`, of KERNEL<c / PER> for c = 64 or 128 (`dtype`, `c`, `st`: the caller's)
+#define C1_LAUNCH_T(KERNEL, grid, lds, ...)                                                                \
+  do {                                                                                                     \
+    if (dtype == GI_F16) hipLaunchKernelGGL(KERNEL<half_t>, dim3(grid), dim3(256), lds, st, __VA_ARGS__);  \
+    else hipLaunchKernelGGL(KERNEL<float>, dim3(grid), dim3(256), lds, st, __VA_ARGS__);                   \
+  } while (0)
+#define C1_LAUNCH_C(KERNEL, PER, grid, lds, ...)                                                           \
+  do {                                                                                                     \
+    if (c == 128) hipLaunchKernelGGL(KERNEL<128 / PER>, dim3(grid), dim3(256), lds, st, __VA_ARGS__);      \
+    else hipLaunchKernelGGL(KERNEL<64 / PER>, dim3(grid), dim3(256), lds, st, __VA_ARGS__);                \
+  } while (0)
 
 int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, void* out, int n, int Hs, int Ws, int c,
                  int ldout, int coffout, int act_out, float in_scale, const float* bias, unsigned long long* bits, int* bits_written) {
@@ -1561,13 +997,11 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
     const int grid = grid_for(ngroups, 4, 256 * 8);
     unsigned long long* const bw = c == 64 ? bits : nullptr;   // (the sign words cover 64 channels)
     if (bw && bits_written) *bits_written = 1;
-#define GI_C1G(MTC_, ACT_) hipLaunchKernelGGL((c1_gather_mfma_kernel<MTC_, ACT_>), dim3(grid), dim3(256), 0, st, img, w, (char*)out, n, Hs, Ws, ldout, coffout, in_scale, bw)
-    if (c == 64) {
-      if (act_out == GI_ACT_LRELU) GI_C1G(4, GI_ACT_LRELU); else if (act_out == GI_ACT_RELU) GI_C1G(4, GI_ACT_RELU); else GI_C1G(4, GI_ACT_NONE);
-    } else {
-      if (act_out == GI_ACT_LRELU) GI_C1G(8, GI_ACT_LRELU); else if (act_out == GI_ACT_RELU) GI_C1G(8, GI_ACT_RELU); else GI_C1G(8, GI_ACT_NONE);
-    }
+#define GI_C1G_(MTC_, ACT_) hipLaunchKernelGGL((c1_gather_mfma_kernel<MTC_, ACT_>), dim3(grid), dim3(256), 0, st, img, w, (char*)out, n, Hs, Ws, ldout, coffout, in_scale, bw)
+#define GI_C1G(ACT_) do { if (c == 64) GI_C1G_(4, ACT_); else GI_C1G_(8, ACT_); } while (0)
+    if (act_out == GI_ACT_LRELU) GI_C1G(GI_ACT_LRELU); else if (act_out == GI_ACT_RELU) GI_C1G(GI_ACT_RELU); else GI_C1G(GI_ACT_NONE);
 #undef GI_C1G
+#undef GI_C1G_
     GI_LAUNCH_CHECK();
     gi_note_kernel(c == 64 ? "c1_gather_mfma<4>" : "c1_gather_mfma<8>");
     return GI_OK;
@@ -1577,12 +1011,7 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
     const int64_t nstrips = (int64_t)n * Hs * (Ws / S);
     const int grid = (int)(nstrips < 256 * 8 ? nstrips : 256 * 8);
     const size_t lds = (size_t)(16 * c + 2 * 4 * (2 * S + 2)) * 4;
-    if (dtype == GI_F16)
-      hipLaunchKernelGGL(c1_gather_strip_kernel<half_t>, dim3(grid), dim3(256), lds, st, img, w, (char*)out, n, Hs, Ws, c, ldout,
-                         coffout, act_out, in_scale, bias);
-    else
-      hipLaunchKernelGGL(c1_gather_strip_kernel<float>, dim3(grid), dim3(256), lds, st, img, w, (char*)out, n, Hs, Ws, c, ldout,
-                         coffout, act_out, in_scale, bias);
+    C1_LAUNCH_T(c1_gather_strip_kernel, grid, lds, img, w, (char*)out, n, Hs, Ws, c, ldout, coffout, act_out, in_scale, bias);
     GI_LAUNCH_CHECK();
     gi_note_kernel("c1_gather_strip");
     return GI_OK;
@@ -1590,12 +1019,7 @@ int op_c1_gather(hipStream_t st, int dtype, const float* img, const float* w, vo
   // the generic form splits a thread index into (pixel, 8-channel group) with a mask and a shift
   GI_REQUIRE(gi_is_pow2(groups), "c1_gather: c=%d unsupported here (c / 8 must be a power of two)", c);
   const int grid = grid_for(total, 256, 256 * 16);
-  if (dtype == GI_F16)
-    hipLaunchKernelGGL(c1_gather_kernel<half_t>, dim3(grid), dim3(256), c * 16 * 4, st, img, w, (char*)out, n, Hs, Ws, c,
-                       ldout, coffout, act_out, in_scale, bias);
-  else
-    hipLaunchKernelGGL(c1_gather_kernel<float>, dim3(grid), dim3(256), c * 16 * 4, st, img, w, (char*)out, n, Hs, Ws, c,
-                       ldout, coffout, act_out, in_scale, bias);
+  C1_LAUNCH_T(c1_gather_kernel, grid, c * 16 * 4, img, w, (char*)out, n, Hs, Ws, c, ldout, coffout, act_out, in_scale, bias);
   GI_LAUNCH_CHECK();
   gi_note_kernel("c1_gather");
   return GI_OK;
@@ -1638,16 +1062,8 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
   if (dtype == GI_F16 && col_scratch && (c == 64 || c == 128) && ldx % 8 == 0 && coffx % 8 == 0) {
     const int64_t P = (int64_t)n * Hs * Ws;
     const int grid = grid_for((P + 15) / 16, 4, 256 * 8);
-    const char* x2 = aff ? (const char*)aff->x2 : nullptr;
-    const int ld2 = aff ? aff->ld2 : 0;
-    const float* sc2 = aff ? aff->scale : nullptr;
-    const float* sh2 = aff ? aff->shift : nullptr;
-    BnAccP fa = {};
-    const int use_fa = (aff && aff->bn) ? 1 : 0;
-    if (use_fa) {
-      GI_REQUIRE(aff->bn->groups == 1, "c1_scatter: one BatchNorm population expected");
-      gi_fill_acc_params(fa, *aff->bn);
-    }
+    GI_REQUIRE(!(aff && aff->bn) || aff->bn->groups == 1, "c1_scatter: one BatchNorm population expected");
+    const C1AffineP u = c1_affine_p(aff);
     // one launch (c1_scatter_fused_kernel) where a band of rows fits LDS; GI_C1_FUSED=0: the col tensor + the overlap-add launch
     int TH = 1024 / Ws;
     if (TH < 1) TH = 1;
@@ -1655,20 +1071,13 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
     const size_t lds_f = (size_t)(TH + 2) * Ws * 32 + 2 * (c / 2) * sizeof(float);
     if (gi_opt(GI_OPT_C1_FUSED) && Ws % 16 == 0 && lds_f <= 64 * 1024 && (int64_t)n * ((Hs + TH - 1) / TH) < (1ll << 31)) {
       const int gridf = n * ((Hs + TH - 1) / TH);
-      if (c == 128)
-        hipLaunchKernelGGL(c1_scatter_fused_kernel<4>, dim3(gridf), dim3(256), lds_f, st, (const char*)X, w, bias, img, img2, Hs, Ws, TH, ldx, coffx, relu_in,
-                           x2, ld2, sc2, sh2, fa, use_fa, post, out_scale);
-      else
-        hipLaunchKernelGGL(c1_scatter_fused_kernel<2>, dim3(gridf), dim3(256), lds_f, st, (const char*)X, w, bias, img, img2, Hs, Ws, TH, ldx, coffx, relu_in,
-                           x2, ld2, sc2, sh2, fa, use_fa, post, out_scale);
+      C1_LAUNCH_C(c1_scatter_fused_kernel, 32, gridf, lds_f, (const char*)X, w, bias, img, img2, Hs, Ws, TH, ldx, coffx, relu_in, u.x2, u.ld2, u.sc2, u.sh2,
+                  u.fa, u.use_fa, post, out_scale);
       GI_LAUNCH_CHECK();
       gi_note_kernel(c == 128 ? "c1_scatter_fused<4>" : "c1_scatter_fused<2>");
       return GI_OK;
     }
-    if (c == 128)
-      hipLaunchKernelGGL(c1_col_kernel<4>, dim3(grid), dim3(256), 0, st, (const char*)X, w, (half_t*)col_scratch, P, ldx, coffx, relu_in, x2, ld2, sc2, sh2, fa, use_fa);
-    else
-      hipLaunchKernelGGL(c1_col_kernel<2>, dim3(grid), dim3(256), 0, st, (const char*)X, w, (half_t*)col_scratch, P, ldx, coffx, relu_in, x2, ld2, sc2, sh2, fa, use_fa);
+    C1_LAUNCH_C(c1_col_kernel, 32, grid, 0, (const char*)X, w, (half_t*)col_scratch, P, ldx, coffx, relu_in, u.x2, u.ld2, u.sc2, u.sh2, u.fa, u.use_fa);
     GI_LAUNCH_CHECK();
     hipLaunchKernelGGL(c1_col2im_kernel, dim3(grid_for(P, 256, 256 * 8)), dim3(256), 0, st, (const half_t*)col_scratch, bias, img, img2, n, Hs,
                        Ws, post, out_scale);
@@ -1681,12 +1090,7 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
   GI_REQUIRE(c % epc == 0 && gi_is_pow2(lpp) && lpp <= 64, "c1_scatter: c=%d unsupported", c);
   const int64_t total = (int64_t)n * Hs * Ws;
   const int grid = grid_for(total, 256 / lpp, 256 * 8);
-  if (dtype == GI_F16)
-    hipLaunchKernelGGL(c1_scatter_kernel<half_t>, dim3(grid), dim3(256), 0, st, (const char*)X, w, bias, img, n, Hs, Ws,
-                       c, ldx, coffx, relu_in, post, out_scale);
-  else
-    hipLaunchKernelGGL(c1_scatter_kernel<float>, dim3(grid), dim3(256), 0, st, (const char*)X, w, bias, img, n, Hs, Ws, c,
-                       ldx, coffx, relu_in, post, out_scale);
+  C1_LAUNCH_T(c1_scatter_kernel, grid, 0, (const char*)X, w, bias, img, n, Hs, Ws, c, ldx, coffx, relu_in, post, out_scale);
   GI_LAUNCH_CHECK();
   if (img2) GI_HIP(hipMemcpyAsync(img2, img, (size_t)n * 4 * Hs * Ws * 4, hipMemcpyDeviceToDevice, st));
   gi_note_kernel("c1_scatter");
@@ -1696,10 +1100,6 @@ int op_c1_scatter(hipStream_t st, int dtype, const void* X, const float* w, cons
 int op_c1_wgrad(hipStream_t st, int dtype, const void* X, const float* img, float* dW, int n, int Hs, int Ws, int c,
                 int ldx, int coffx, int relu_in, float scale, float img_scale, const C1Affine* aff, float* scratch, int64_t scratch_floats) {
   GI_REQUIRE(!aff || (op_c1_affine_ok(dtype, c, Ws, ldx, coffx) && aff->ld2 % 8 == 0), "c1_wgrad: fused upper half unsupported here");
-  const char* x2 = aff ? (const char*)aff->x2 : nullptr;
-  const int ld2 = aff ? aff->ld2 : 0;
-  const float* sc2 = aff ? aff->scale : nullptr;
-  const float* sh2 = aff ? aff->shift : nullptr;
   if (dtype == GI_F16 && (c == 64 || c == 128) && Ws % 32 == 0 && ldx % 8 == 0 && coffx % 8 == 0) {
     const int64_t ntiles = (int64_t)n * Hs * Ws / 32;
     GI_REQUIRE(ntiles < (1ll << 31), "c1_wgrad: %lld pixel tiles", (long long)ntiles);
@@ -1709,12 +1109,9 @@ int op_c1_wgrad(hipStream_t st, int dtype, const void* X, const float* img, floa
     size_t lds = (size_t)4 * 32 * (c * 2 + 32);
     if (lds < (size_t)4 * c * 16 * 4) lds = (size_t)4 * c * 16 * 4;
     float* part = (scratch && scratch_floats >= (int64_t)grid * c * 16) ? scratch : nullptr;   // deterministic two-stage sum
-    if (c == 64)
-      hipLaunchKernelGGL(c1_wgrad_mfma_kernel<4>, dim3(grid), dim3(256), lds, st, (const char*)X, img, dW, n, Hs, Ws, ldx, coffx, relu_in,
-                         scale, img_scale, x2, ld2, sc2, sh2, part);
-    else
-      hipLaunchKernelGGL(c1_wgrad_mfma_kernel<8>, dim3(grid), dim3(256), lds, st, (const char*)X, img, dW, n, Hs, Ws, ldx, coffx, relu_in,
-                         scale, img_scale, x2, ld2, sc2, sh2, part);
+    const C1AffineP u = c1_affine_p(aff);   // (the vectors exist by now: u.fa is not used)
+    C1_LAUNCH_C(c1_wgrad_mfma_kernel, 16, grid, lds, (const char*)X, img, dW, n, Hs, Ws, ldx, coffx, relu_in, scale, img_scale, u.x2, u.ld2, u.sc2, u.sh2,
+                part);
     GI_LAUNCH_CHECK();
     if (part) {
       hipLaunchKernelGGL(c1_wgrad_reduce_kernel, dim3((c * 16 + 15) / 16), dim3(256), 0, st, (const float*)part, dW, c * 16, grid);
@@ -1734,12 +1131,7 @@ int op_c1_wgrad(hipStream_t st, int dtype, const void* X, const float* img, floa
   const int grid = (int)((total + ppb - 1) / ppb);
   const size_t lds = (size_t)gpb * c * 4 * 4;
   float* part = (scratch && scratch_floats >= (int64_t)grid * c * 16) ? scratch : nullptr;   // deterministic two-stage sum
-  if (dtype == GI_F16)
-    hipLaunchKernelGGL(c1_wgrad_kernel<half_t>, dim3(grid), dim3(256), lds, st, (const char*)X, img, dW, n, Hs, Ws, c,
-                       ldx, coffx, relu_in, scale, img_scale, ppb, part);
-  else
-    hipLaunchKernelGGL(c1_wgrad_kernel<float>, dim3(grid), dim3(256), lds, st, (const char*)X, img, dW, n, Hs, Ws, c, ldx,
-                       coffx, relu_in, scale, img_scale, ppb, part);
+  C1_LAUNCH_T(c1_wgrad_kernel, grid, lds, (const char*)X, img, dW, n, Hs, Ws, c, ldx, coffx, relu_in, scale, img_scale, ppb, part);
   GI_LAUNCH_CHECK();
   if (part) {
     hipLaunchKernelGGL(c1_wgrad_reduce_kernel, dim3((c * 16 + 15) / 16), dim3(256), 0, st, (const float*)part, dW, c * 16, grid);
@@ -1748,108 +1140,8 @@ int op_c1_wgrad(hipStream_t st, int dtype, const void* X, const float* img, floa
   gi_note_kernel(part ? "c1_wgrad" : "c1_wgrad,atomics");
   return GI_OK;
 }
-
-int op_head_forward(hipStream_t st, int dtype, const HeadArgs& a) {
-  const int Ph = a.Hh - 3, Pw = a.Wh - 3;
-  GI_REQUIRE(Ph >= 1 && Pw >= 1, "head: feature map %dx%d too small", a.Hh, a.Wh);
-  const int blocks = a.n * Ph * Pw;
-  GI_REQUIRE(!a.scale4 || op_head_affine_ok(dtype, a.c), "head: fused BatchNorm input needs the fp16 c=512 kernels");
-  GI_REQUIRE(!a.bn || (a.scale4 && dtype == GI_F16 && a.c == 512 && head_fast()), "head: accumulator-derived BatchNorm needs the fused fp16 c=512 path");
-  if (dtype == GI_F16 && a.c == 512 && head_fast()) {
-    BnAccP fa = {};
-    const int use_fa = a.bn ? 1 : 0;
-    if (use_fa) {
-      gi_fill_acc_params(fa, *a.bn);
-      GI_REQUIRE(fa.out_stride == a.gstride, "head: population stride %d != %d", fa.out_stride, a.gstride);
-    }
-    const int lds = (((a.Hh * a.Wh * HT_PITCH + 3) & ~3) + 16) * 4 + 16 * 512 * 2 + 2 * 512 * 4;
-    GI_REQUIRE(lds <= 160 * 1024, "head: feature map %dx%d too large", a.Hh, a.Wh);
-    if (lds > 64 * 1024) {
-      static GiDevOnce attr;
-      if (attr.first()) { GI_HIP(hipFuncSetAttribute((const void*)head_fwd512_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
-    }
-    // large maps with few images (512x512 inputs: 32x32 map, 64 tiles per image): slice each image over several
-    // workgroups so that ~256 of them stream the activations, and finish in a second small kernel
-    const int npx = a.Hh * a.Wh;
-    int slices = 1;
-    while (a.n * slices < 256 && npx / (slices * 2) >= 256) slices *= 2;
-    if (slices > 1 && a.tbuf && a.tbuf_bytes >= (int64_t)a.n * npx * 16 * 4) {
-      const int lds2 = (16) * 4 + 16 * 512 * 2 + 2 * 512 * 4;
-      hipLaunchKernelGGL(head_fwd512_kernel, dim3(a.n * slices), dim3(1024), lds2, st, (const char*)a.a4, a.w5, a.wl, a.bl, a.h, a.out, a.out2, a.Hh,
-                         a.Wh, a.sigmoid, a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, a.tbuf, slices, fa, use_fa);
-      GI_LAUNCH_CHECK();
-      hipLaunchKernelGGL(head_h512_kernel, dim3(a.n), dim3(256), 0, st, a.tbuf, a.wl, a.bl, a.h, a.out, a.out2, a.Hh, a.Wh, a.sigmoid);
-      GI_LAUNCH_CHECK();
-      return GI_OK;
-    }
-    hipLaunchKernelGGL(head_fwd512_kernel, dim3(a.n), dim3(1024), lds, st, (const char*)a.a4, a.w5, a.wl, a.bl, a.h, a.out, a.out2, a.Hh, a.Wh, a.sigmoid,
-                       a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, (float*)nullptr, 1, fa, use_fa);
-    GI_LAUNCH_CHECK();
-    return GI_OK;
-  }
-  if (dtype == GI_F16)
-    hipLaunchKernelGGL(head_conv_kernel<half_t>, dim3(blocks), dim3(256), 0, st, (const char*)a.a4, a.w5, a.h, a.Hh, a.Wh, a.c);
-  else
-    hipLaunchKernelGGL(head_conv_kernel<float>, dim3(blocks), dim3(256), 0, st, (const char*)a.a4, a.w5, a.h, a.Hh, a.Wh, a.c);
-  GI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_linear_kernel, dim3(a.n), dim3(64), 0, st, a.h, a.wl, a.bl, a.out, Ph * Pw, a.sigmoid);
-  GI_LAUNCH_CHECK();
-  if (a.out2) GI_HIP(hipMemcpyAsync(a.out2, a.out, (size_t)a.n * 4, hipMemcpyDeviceToDevice, st));
-  return GI_OK;
-}
-
-int op_head_backward(hipStream_t st, int dtype, const HeadBwdArgs& a) {
-  const int Ph = a.Hh - 3, Pw = a.Wh - 3, P = Ph * Pw;
-  GI_REQUIRE(!a.scale4 || (op_head_affine_ok(dtype, a.c) && (!a.dw5 || (a.scratch && a.scratch_bytes >= (int64_t)a.n * head_bands(a.n, a.Hh * a.Wh) * 8192 * 4))),
-             "head: fused BatchNorm input needs the fp16 c=512 kernels");
-  if (dtype == GI_F16 && a.c == 512 && head_fast()) {
-    const int bands = head_bands(a.n, a.Hh * a.Wh), nb = a.n * bands;
-    const bool wg = a.dw5 != nullptr;
-    HeadBwdFuse hf;
-    hf.x = (const char*)a.bwd_x; hf.scale = a.bwd_scale; hf.shift = a.bwd_shift; hf.mean = a.bwd_mean; hf.inv = a.bwd_inv;
-    hf.stride = a.bwd_stride; hf.n_per_group = a.bwd_n_per_group > 0 ? a.bwd_n_per_group : a.n; hf.reps = a.bwd_reps > 0 ? a.bwd_reps : 1;
-    hf.slope = a.bwd_slope; hf.acc = (a.bwd_acc && a.bwd_x) ? a.bwd_acc : nullptr;
-    if (!wg || (a.scratch && a.scratch_bytes >= (int64_t)nb * 8192 * 4)) {
-      GI_REQUIRE(!wg || a.dwl, "head: dw5 without dwl");
-      hipLaunchKernelGGL(head_bwd512_kernel, dim3(wg ? 2 * nb : nb), dim3(256), 0, st, a.dy, a.out, a.h, a.wl, a.w5, (const char*)a.a4,
-                         (char*)a.da4, a.scratch, a.dwl, a.dbl, a.n, a.Hh, a.Wh, bands, a.sigmoid, a.loss_scale,
-                         a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, hf);
-      GI_LAUNCH_CHECK();
-      if (hf.acc && a.bwd_applied) *a.bwd_applied = 1;
-      if (wg) {
-        hipLaunchKernelGGL(head_wsum512_kernel, dim3(256 + P + 1), dim3(256), 0, st, a.scratch, nb, a.dw5, a.dy, a.out, a.h, a.dwl, a.dbl, a.n, P, a.sigmoid);
-        GI_LAUNCH_CHECK();
-      }
-      return GI_OK;
-    }
-  }
-  hipLaunchKernelGGL(head_linear_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, st, a.dy, a.out, a.h, a.wl, a.dh, a.dwl,
-                     a.dbl, a.n, P, a.sigmoid);
-  GI_LAUNCH_CHECK();
-  const int epc = dtype == GI_F16 ? 8 : 4;
-  const int64_t total = (int64_t)a.n * a.Hh * a.Wh * (a.c / epc);
-  const int grid = grid_for(total, 256, 4096);
-  if (dtype == GI_F16)
-    hipLaunchKernelGGL(head_dgrad_kernel<half_t>, dim3(grid), dim3(256), 0, st, a.dh, a.w5, (char*)a.da4, a.n, a.Hh, a.Wh, a.c, a.loss_scale);
-  else
-    hipLaunchKernelGGL(head_dgrad_kernel<float>, dim3(grid), dim3(256), 0, st, a.dh, a.w5, (char*)a.da4, a.n, a.Hh, a.Wh, a.c, a.loss_scale);
-  GI_LAUNCH_CHECK();
-  if (a.dw5) {
-    dim3 g((16 * (a.c / epc) + 255) / 256, a.n, Ph >= 8 ? 2 : 1);
-    const int nparts = a.n * (int)g.z;
-    float* part = (a.scratch && a.scratch_bytes >= (int64_t)nparts * 16 * a.c * 4) ? a.scratch : nullptr;
-    if (dtype == GI_F16)
-      hipLaunchKernelGGL(head_wgrad_kernel<half_t>, g, dim3(256), 0, st, a.dh, (const char*)a.a4, a.dw5, a.Hh, a.Wh, a.c, part);
-    else
-      hipLaunchKernelGGL(head_wgrad_kernel<float>, g, dim3(256), 0, st, a.dh, (const char*)a.a4, a.dw5, a.Hh, a.Wh, a.c, part);
-    GI_LAUNCH_CHECK();
-    if (part) {
-      hipLaunchKernelGGL(head_wgrad_sum_kernel, dim3((16 * a.c + 255) / 256), dim3(256), 0, st, part, nparts, a.dw5, 16 * a.c);
-      GI_LAUNCH_CHECK();
-    }
-  }
-  return GI_OK;
-}
+#undef C1_LAUNCH_T
+#undef C1_LAUNCH_C
 
 // The 4-channel head of a narrow generator (fp16, c = 128 input channels): forward (col + col2im, bias + tanh) and input gradient.
 bool op_c1_head4_ok(int dtype, int c, int out_c, int Ws, int ldx, int coffx) {

@@ -206,6 +206,13 @@ static inline int gi_ilog2(int v) {
   return l;
 }
 static inline bool gi_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// workgroups for work_items items at per_block each: at least 1, at most cap (persistent loops cover the rest)
+static inline int grid_for(int64_t work_items, int per_block, int cap) {
+  int64_t b = (work_items + per_block - 1) / per_block;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
 
 // ------------------------------------------------------------------------------------------
 // kernel launch wrappers (ops_*.hip). All tensors NHWC, element type T selected by dtype.
@@ -297,7 +304,7 @@ struct WgradArgs {
 int op_wgrad(hipStream_t st, int dtype, const WgradArgs& a);
 int64_t op_wgrad_scratch_bytes(int dtype, int n, int Hs, int Ws, int ca, int cb);
 
-// single-channel-side kernels (generator first conv / last transposed conv, discriminator first
+// single-channel-side kernels (c1.hip: generator first conv / last transposed conv, discriminator first
 // conv): weights fp32 [c][16] (= [a][ky][kx][b] with b == 1)
 // out[p][c] = act(sum_tap img[n,2y-1+ky,2x-1+kx] * w[c][tap])      img fp32 (n,2Hs,2Ws)
 // bits != null: the kernels that can also write one 64-bit sign word per pixel (bit c = [out[p][c] > 0], c = 64 only) and say so
@@ -418,7 +425,7 @@ int op_act_in_bwd(hipStream_t st, int dtype, const ActBnBwdArgs& a, int n, int h
 // dbias[ch] += scale * sum_pixels dz[p][ch]; partials: scratch for the column pass ((pixels/32 + 8) * 2 * c floats)
 int op_bias_grad(hipStream_t st, int dtype, const void* dz, int64_t pixels, int c, float scale, float* dbias, float* partials);   // rows one reduce workgroup covers (groups = 2 needs pixels/2 to be a multiple)
 
-// discriminator head: conv(512->1,k4,s1,p0) + Flatten + Linear(P,1) [+ sigmoid]
+// discriminator head (head.hip): conv(512->1,k4,s1,p0) + Flatten + Linear(P,1) [+ sigmoid]
 struct HeadArgs {
   const void* a4;      // (n,Hh,Wh,c) T dense
   const float* w5;     // [16][c]  (= [1][ky][kx][c])

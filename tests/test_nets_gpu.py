@@ -291,7 +291,7 @@ def test_patchgan_gradients_are_reproducible(dtype):
 
 @pytest.mark.parametrize("cfg", [(64, 5), (256, 4), (512, 1)])
 def test_patchgan_head_gradients_are_reproducible(cfg):
-    """fp16 head kernels (csrc/c1.hip: head_fwd512 / head_bwd512 / head_wsum512): the weight-gradient partials are
+    """fp16 head kernels (csrc/head.hip: head_fwd512 / head_bwd512 / head_wsum512): the weight-gradient partials are
     summed in a fixed order, so the head's parameter gradients and the network output repeat bit for bit
     (the 4x4, 16x16 and 32x32 feature maps: one tile, LDS-resident map, dynamic-LDS path above 64 KiB)."""
     HW, N = cfg
