@@ -122,6 +122,7 @@ PROTOTYPES = {
     "gi_resize_build_tables": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "gi_resize_to_tensor": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gi_mask_generate": (_i, [_vp, _i, _u64, _vp, _i, _i, _i, _vp, _vp]),
+    "gi_batch_gather": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _u64, _i, _vp]),
     "gi_check_finite": (_i, [_vp, _vp, _i64, _vp]),
     "gi_check_finite_scan": (_i, [_vp, _vp, _i64, _vp]),
     "gi_check_finite_finish": (_i, [_vp, _vp]),

@@ -153,7 +153,10 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
         acc_g = torch.zeros(len(flow_G.names), device=device)
         with _on(side):
             acc_d = [torch.zeros(len(f.names), device=device) for f in flows_D]
-        for bi, (ground, mask, extra) in enumerate(loaders["train"]):
+        train = loaders["train"]
+        if state.get("flip") and hasattr(train, "augmented"):     # --flip: the cached loader's pass with this epoch's flips
+            train = train.augmented(epoch)
+        for bi, (ground, mask, extra) in enumerate(train):
             ground = to_device_images(ground, device, state)
             mask = to_device_mask(mask, ground, device, state, "train", epoch)
             if pass_extra:

@@ -5,7 +5,7 @@ on the HIP backend. The reference launcher does not run as written (SURVEY.md se
 variable names at :173,:180,:183 and a hard-coded dataset path :64); this one iterates over
 --experiments as evidently intended and takes the data as --data synthetic (the benchmark's masked-
 image batches) or --data <dir> in the reference's dataset layout (csv/train_all_masks.csv, csv/test_all_masks.csv listing image
-files; decoded on the host with PIL, resized + normalised on the device). FID statistics (train.py:157-166) are computed on the device when
+files; decoded on the host with PIL, resized + normalised on the device - per batch, or once into a device-resident cache with --cache device). FID statistics (train.py:157-166) are computed on the device when
 --fid-weights names a local copy of the published Inception state dict (never downloaded); the face-segmentation checkpoint (:169-175) is not available (--face-parsing random).
 
     python gan-inpainting_amd/train.py -exp wgan_l1 -ep 2 -b 32 --imagedim 256 --data synthetic
@@ -81,8 +81,22 @@ def load_rows(csv_path, rank, world, batchsize):
     return df
 
 
+class _Parser(argparse.ArgumentParser):
+    """The flags that depend on each other are checked where the others are: in parse_args."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.cache == "device" and a.data == "synthetic":
+            self.error("--cache device needs --data <dir> (synthetic batches are not decoded from files)")
+        if a.flip and a.cache != "device":
+            self.error("--flip needs --cache device (the flips happen where the cached batches are assembled)")
+        if a.cache_budget_gb is not None and a.cache_budget_gb <= 0:
+            self.error("--cache-budget-gb must be positive")
+        return a
+
+
 def build_parser():
-    parser = argparse.ArgumentParser()
+    parser = _Parser()
     parser.add_argument("-exp", "--experiments", nargs="+", required=True)
     parser.add_argument("-ep", "--numepoch", type=int, default=1500)
     parser.add_argument("-b", "--batchsize", type=int, default=128)
@@ -114,6 +128,14 @@ def build_parser():
                              "--data synthetic). rect / freeform: generated on the device per sample (lib/data/masks.py): "
                              "the CSVs need no mask_source column, test masks are the same in every epoch, training masks change")
     parser.add_argument("--mask-seed", dest="mask_seed", type=int, default=0, help="seed of the generated masks")
+    parser.add_argument("--cache", choices=["off", "device"], default="off",
+                        help="device: decode and resize every file of --data <dir> once, keep the resized bytes on the device and "
+                             "assemble every batch there (lib/data/cache.py); each rank caches its own shard")
+    parser.add_argument("--flip", action="store_true", default=False,
+                        help="random horizontal flips of the training images (and their segment maps), per (epoch, row) under "
+                             "--mask-seed; needs --cache device. Evaluation and FID statistics see the data as stored")
+    parser.add_argument("--cache-budget-gb", dest="cache_budget_gb", type=float, default=None,
+                        help="device memory the cache may take (default: half of what is free when it is built)")
     parser.add_argument("--samples", type=int, default=1024)
     parser.add_argument("--outdir", default=os.path.join(os.getcwd(), "runs"))
     parser.add_argument("--perceptual-grad", dest="perceptual_grad", action="store_true", default=False,
@@ -144,6 +166,13 @@ def main(argv=None):
 
         def mk_real(csv, shuffle):
             df = load_rows(os.path.join(args.data, "csv", csv), rank, world, args.batchsize)
+            if args.cache == "device":
+                from gan_inpainting_amd.lib.data import cache as dcache
+                budget = None if args.cache_budget_gb is None else int(args.cache_budget_gb * 2 ** 30)
+                store = dcache.DeviceImageCache.build(
+                    dataset.InpaintingDataset(args.data, dataframe=df, transform=None, masks="generated" if generated else "files"),
+                    args.imagedim, torch.device("cuda", torch.cuda.current_device()), workers=args.workers, budget_bytes=budget)
+                return dcache.DeviceCachedLoader(store, args.batchsize, csv.split("_")[0], flip_seed=args.mask_seed)
             return torch.utils.data.DataLoader(dataset.InpaintingDataset(args.data, dataframe=df, transform=None,
                                                                          masks="generated" if generated else "files"),
                                                batch_size=args.batchsize, shuffle=shuffle, drop_last=True, **lkw)

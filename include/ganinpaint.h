@@ -461,6 +461,18 @@ int gi_resize_to_tensor(gi_ctx* ctx, const void* tables_dev, const uint8_t* src,
 int gi_mask_generate(gi_ctx* ctx, int kind, uint64_t seed, const int64_t* keys_dev, int n, int H, int W, float* mask_out,
                      int* coverage_out);
 
+/* ---- batch assembly from a device-resident image store (lib/data/cache.py): store is (n_store,h,w) uint8 on
+ *      the device, rows_dev n int64 on the device, out (n,h,w) of out_kind: 0 fp32 (float)v / 255.0f (the ToTensor quotient of
+ *      gi_resize_to_tensor), 1 int64 v (segmentation labels), 2 uint8 v. out[i][y][x] = f(store[rows[i]][y][flip_i ? w-1-x : x]).
+ *      flip_keys_dev (n int64 on the device; NULL: no flips): flip_i = mix(stream + G) >> 63 with
+ *      stream = mix((flip_seed ^ 0x666C6970) + G * (key_i + 1)) on the dropout hash, independent of the mask draws of the same
+ *      key (tests/batchgather_ref.py is the numpy restatement, bit-exact with this entry). A row outside [0, n_store) reads
+ *      nothing and yields zeros. out is aligned to its element; 16-byte alignment (4 for uint8) with w % 4 == 0 takes the
+ *      vector path. h * w < 2^31. Invalid arguments return GI_ERR_INVALID before anything is launched; asynchronous on the
+ *      context's stream. */
+int gi_batch_gather(gi_ctx* ctx, const uint8_t* store, int64_t n_store, int h, int w, const int64_t* rows_dev, int n,
+                    const int64_t* flip_keys_dev, uint64_t flip_seed, int out_kind, void* out);
+
 /* ---- single-layer entry points (unit parity tests and kernel roofline measurements) -------- */
 /* out[n,y,x,a] = act( sum_{ky,kx,b} in[n,2y-1+ky,2x-1+kx,b] * w[a][ky][kx][b] ), NHWC, dtype T.
  * in: (n,H,W,cb) ld=ldin; out: (n,H/2,W/2,ca) ld=ldout. w_packed is T [ca][16*cb].
