@@ -149,6 +149,23 @@ PROTOTYPES = {
     "gi_debug_igemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp, _i, _vp]),
     "gi_stat_acc_words": (_i64, [_i]),
     "gi_stat_acc_read": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "gi_debug_col_stats": (_i, [_vp, _i, _vp, _i64, _i, _vp, C.POINTER(_i)]),
+    "gi_debug_bn_finalize": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _i64, _i]),
+    "gi_debug_bn_apply": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _f, _i64, _i]),
+    "gi_debug_bn_finalize_acc": (_i, [_vp, _i, _vp]),
+    "gi_debug_bn_apply_acc": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _f, _u64, _f, _vp, _vp, _vp, _i64]),
+    "gi_debug_act_bn_bwd": (_i, [_vp, _i, _vp]),
+    "gi_debug_in_forward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _vp]),
+    "gi_debug_act_in_bwd": (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    "gi_debug_bias_grad": (_i, [_vp, _i, _vp, _i64, _i, _f, _vp, _vp]),
+    "gi_debug_tanh_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _f]),
+    "gi_debug_fill_dropout": (_i, [_vp, _vp, _i64, _u64, _f]),
+    "gi_debug_mask_layout": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "gi_debug_mul_slope": (_i, [_vp, _i, _vp, _vp, _vp, _i64]),
+    "gi_debug_bn_tangent_inject": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "gi_debug_gp_direction": (_i, [_vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gi_debug_gp_unscale_add": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "gi_debug_stat_acc_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
     "gi_pack_weights": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
     "gi_convert": (_i, [_vp, _i, _vp, _vp, _i64]),
     "gi_convert_back": (_i, [_vp, _i, _vp, _vp, _i64]),
@@ -173,6 +190,31 @@ class IgemmEx(C.Structure):
                 ("bwd_slope", _f), ("bwd_acc", _vp), ("bwd_reps", _i), ("bwd_pg", _i64),
                 ("bwd_c0", _i), ("bwd_c", _i),
                 ("mask_applied", _i), ("bwd_applied", _i), ("stat_used", _i), ("ntiles_out", _i)]
+
+
+class BnAccArgs(C.Structure):
+    """gi_bn_acc_args (include/ganinpaint.h): BatchNorm from an exact accumulator block (the gi_debug_bn_*_acc entries)."""
+    _fields_ = [("acc", _vp), ("reps", _i),
+                ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp),
+                ("scale", _vp), ("shift", _vp), ("save_mean", _vp), ("save_invstd", _vp),
+                ("count", _i64), ("momentum", _f), ("eps", _f), ("groups", _i), ("out_stride", _i),
+                ("zero_next", _vp), ("zero_words", _i)]
+
+
+class ActBnBwdArgs(C.Structure):
+    """gi_act_bn_bwd_args (include/ganinpaint.h): gi_debug_act_bn_bwd / gi_debug_act_in_bwd."""
+    _fields_ = [("g1", _vp), ("ldg1", _i), ("coffg1", _i),
+                ("g2", _vp), ("ldg2", _i), ("coffg2", _i),
+                ("y", _vp), ("ldy", _i), ("coffy", _i),
+                ("x", _vp), ("dx", _vp),
+                ("pixels", _i64), ("c", _i), ("act", _i), ("drop_scale", _f),
+                ("has_bn", _i), ("eval_bn", _i),
+                ("gamma", _vp), ("save_mean", _vp), ("save_invstd", _vp),
+                ("dgamma", _vp), ("dbeta", _vp), ("inv_loss_scale", _f),
+                ("partials", _vp), ("sums", _vp), ("fwd_scale", _vp), ("fwd_shift", _vp),
+                ("groups", _i), ("stat_stride", _i),
+                ("acc", _vp), ("acc_reps", _i), ("zero_next", _vp), ("zero_words", _i),
+                ("reduce_done", _i)]
 
 
 class BackendError(RuntimeError):

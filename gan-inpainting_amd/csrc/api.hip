@@ -313,6 +313,213 @@ int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, in
   return op_c1_head4_dgrad(ctx->stream, g, w, out, n, Hs, Ws, ldout, coffout);
 }
 
+// ---- the normalisation / activation-backward passes (elementwise.hip) on their own: what tests/test_norm_ops_gpu.py drives ------
+namespace {
+inline int dbg_epc(int dtype) { return dtype == GI_F16 ? 8 : 4; }
+inline bool dbg_dtype_ok(int dtype) { return dtype == GI_F16 || dtype == GI_F32; }
+inline bool dbg_act_ok(int act) { return act == GI_ACT_NONE || act == GI_ACT_RELU || act == GI_ACT_LRELU; }
+// c as the chunked passes take it: c / chunk a power of two <= 256
+inline bool dbg_c_ok(int dtype, int c) { const int e = dbg_epc(dtype); return c > 0 && c % e == 0 && gi_is_pow2(c / e) && c / e <= 256; }
+// a (pixels, ld) view at channel offset coff holding c channels, every chunk 16-byte aligned
+inline bool dbg_view_ok(int dtype, int c, int ld, int coff) { const int e = dbg_epc(dtype); return coff >= 0 && coff % e == 0 && ld % e == 0 && coff + c <= ld; }
+
+int dbg_bn_acc(const char* who, int c, const gi_bn_acc_args* b, BnAccArgs& o) {
+  GI_REQUIRE(b && b->acc && b->gamma && b->beta && b->running_mean && b->running_var && b->scale && b->shift && b->save_mean && b->save_invstd,
+             "%s: null pointer", who);
+  GI_REQUIRE(b->reps >= 1 && b->reps <= GI_STAT_MAXREP, "%s: reps=%d outside 1..%d", who, b->reps, GI_STAT_MAXREP);
+  GI_REQUIRE(b->groups == 1 || b->groups == 2, "%s: groups=%d (1 or 2)", who, b->groups);
+  GI_REQUIRE(b->count >= 1, "%s: count=%lld", who, (long long)b->count);
+  GI_REQUIRE(b->groups == 1 || b->out_stride >= c, "%s: out_stride=%d below the %d channels", who, b->out_stride, c);
+  GI_REQUIRE(b->zero_words >= 0 && (b->zero_words == 0 || b->zero_next), "%s: zero_words=%d without zero_next", who, b->zero_words);
+  o.acc = b->acc; o.reps = b->reps; o.gamma = b->gamma; o.beta = b->beta; o.running_mean = b->running_mean; o.running_var = b->running_var;
+  o.scale = b->scale; o.shift = b->shift; o.save_mean = b->save_mean; o.save_invstd = b->save_invstd;
+  o.count = b->count; o.momentum = b->momentum; o.eps = b->eps; o.groups = b->groups; o.out_stride = b->out_stride;
+  o.zero_next = b->zero_words > 0 ? b->zero_next : nullptr; o.zero_words = b->zero_words;
+  return GI_OK;
+}
+
+// the checks shared by the BatchNorm and the InstanceNorm backward, and the copy into ActBnBwdArgs
+int dbg_bwd_args(const char* who, int dtype, const gi_act_bn_bwd_args* s, bool chunks_pow2, ActBnBwdArgs& a) {
+  GI_REQUIRE(s && s->dx, "%s: null pointer", who);
+  GI_REQUIRE(dbg_dtype_ok(dtype) && dbg_act_ok(s->act), "%s: dtype=%d act=%d", who, dtype, s->act);
+  GI_REQUIRE(chunks_pow2 ? dbg_c_ok(dtype, s->c) : (s->c > 0 && s->c % dbg_epc(dtype) == 0), "%s: c=%d unsupported", who, s->c);
+  GI_REQUIRE(s->pixels >= 1, "%s: pixels=%lld", who, (long long)s->pixels);
+  GI_REQUIRE(s->g1 || s->g2, "%s: no upstream gradient", who);
+  GI_REQUIRE(!s->g1 || dbg_view_ok(dtype, s->c, s->ldg1, s->coffg1), "%s: g1 ld=%d coff=%d for %d channels", who, s->ldg1, s->coffg1, s->c);
+  GI_REQUIRE(!s->g2 || dbg_view_ok(dtype, s->c, s->ldg2, s->coffg2), "%s: g2 ld=%d coff=%d for %d channels", who, s->ldg2, s->coffg2, s->c);
+  GI_REQUIRE(!s->y || dbg_view_ok(dtype, s->c, s->ldy, s->coffy), "%s: y ld=%d coff=%d for %d channels", who, s->ldy, s->coffy, s->c);
+  GI_REQUIRE(s->drop_scale == 1.f || s->act == GI_ACT_RELU,
+             "%s: drop_scale=%g with act=%d: the backward takes the dropout zeros from y > 0, which only a ReLU output can carry", who,
+             (double)s->drop_scale, s->act);
+  memset(&a, 0, sizeof(a));
+  a.g1 = s->g1; a.ldg1 = s->ldg1; a.coffg1 = s->coffg1;
+  a.g2 = s->g2; a.ldg2 = s->ldg2; a.coffg2 = s->coffg2;
+  a.y = s->y; a.ldy = s->ldy; a.coffy = s->coffy;
+  a.x = s->x; a.dx = s->dx; a.pixels = s->pixels; a.c = s->c; a.act = s->act; a.drop_scale = s->drop_scale;
+  a.has_bn = s->has_bn; a.eval_bn = s->eval_bn;
+  a.gamma = s->gamma; a.save_mean = s->save_mean; a.save_invstd = s->save_invstd;
+  a.dgamma = s->dgamma; a.dbeta = s->dbeta; a.inv_loss_scale = s->inv_loss_scale;
+  a.partials = s->partials; a.sums = s->sums; a.fwd_scale = s->fwd_scale; a.fwd_shift = s->fwd_shift;
+  a.groups = s->groups; a.stat_stride = s->stat_stride;
+  a.acc = s->acc; a.acc_reps = s->acc_reps; a.zero_next = s->zero_words > 0 ? s->zero_next : nullptr; a.zero_words = s->zero_words;
+  a.reduce_done = s->reduce_done;
+  return GI_OK;
+}
+
+// one workgroup per row, one lane per channel (the lanes of an atomic instruction are consecutive words, stat_acc.h)
+__global__ void __launch_bounds__(256) stat_acc_add_kernel(unsigned long long* acc, int c, int reps, int group, int q, const float* addends) {
+  const int r = blockIdx.x;
+  for (int ch = threadIdx.x; ch < c; ch += 256) gi_stat_add(acc, c, r & (reps - 1), group, q, ch, addends[(int64_t)r * c + ch]);
+}
+}  // namespace
+
+int gi_debug_col_stats(gi_ctx* ctx, int dtype, const void* x, int64_t pixels, int c, float* partials, int* rows_out) {
+  GI_REQUIRE(ctx && x && partials && rows_out, "debug_col_stats: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && pixels >= 1, "debug_col_stats: dtype=%d pixels=%lld", dtype, (long long)pixels);
+  return op_col_stats(ctx->stream, dtype, x, pixels, c, partials, rows_out);
+}
+
+int gi_debug_bn_finalize(gi_ctx* ctx, const float* partials, int rows, int c, int64_t count, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, float* scale, float* shift, float* save_mean, float* save_invstd, int train,
+                         float momentum, float eps, int groups, int64_t part_stride, int out_stride) {
+  GI_REQUIRE(ctx && gamma && beta && running_mean && running_var && scale && shift && save_mean && save_invstd, "debug_bn_finalize: null pointer");
+  GI_REQUIRE(!train || (partials && rows >= 1), "debug_bn_finalize: train mode needs partial rows (rows=%d)", rows);
+  GI_REQUIRE(c >= 1 && count >= 1, "debug_bn_finalize: c=%d count=%lld", c, (long long)count);
+  GI_REQUIRE(groups == 1 || groups == 2, "debug_bn_finalize: groups=%d (1 or 2)", groups);
+  GI_REQUIRE(groups == 1 || (out_stride >= c && (!train || part_stride >= (int64_t)rows * 2 * c)),
+             "debug_bn_finalize: two populations overlap (part_stride=%lld out_stride=%d)", (long long)part_stride, out_stride);
+  return op_bn_finalize(ctx->stream, partials, rows, c, count, gamma, beta, running_mean, running_var, scale, shift, save_mean, save_invstd, train,
+                        momentum, eps, groups, part_stride, out_stride);
+}
+
+int gi_debug_bn_apply(gi_ctx* ctx, int dtype, const void* x, void* y, int64_t pixels, int c, int ldy, int coffy, const float* scale,
+                      const float* shift, int act, const uint8_t* drop_mask, float drop_scale, int64_t pg, int gstride) {
+  GI_REQUIRE(ctx && x && y, "debug_bn_apply: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && dbg_act_ok(act) && pixels >= 1, "debug_bn_apply: dtype=%d act=%d pixels=%lld", dtype, act, (long long)pixels);
+  GI_REQUIRE(dbg_c_ok(dtype, c), "debug_bn_apply: c=%d unsupported", c);
+  GI_REQUIRE(dbg_view_ok(dtype, c, ldy, coffy), "debug_bn_apply: ldy=%d coffy=%d for %d channels", ldy, coffy, c);
+  GI_REQUIRE((scale == nullptr) == (shift == nullptr), "debug_bn_apply: scale and shift go together");
+  GI_REQUIRE(pg >= 0 && pg <= pixels, "debug_bn_apply: pg=%lld of %lld pixels", (long long)pg, (long long)pixels);
+  GI_REQUIRE(!(pg > 0 && pg < pixels) || gstride >= c, "debug_bn_apply: gstride=%d below the %d channels", gstride, c);
+  return op_bn_apply(ctx->stream, dtype, x, y, pixels, c, ldy, coffy, scale, shift, act, drop_mask, drop_scale, pg, gstride);
+}
+
+int gi_debug_bn_finalize_acc(gi_ctx* ctx, int c, const gi_bn_acc_args* b) {
+  GI_REQUIRE(ctx && c >= 1, "debug_bn_finalize_acc: bad argument");
+  BnAccArgs o;
+  GI_TRY(dbg_bn_acc("debug_bn_finalize_acc", c, b, o));
+  return op_bn_finalize_acc(ctx->stream, c, o);
+}
+
+int gi_debug_bn_apply_acc(gi_ctx* ctx, int dtype, const void* x, void* y, int64_t pixels, int c, int ldy, int coffy, int act, uint8_t* drop_mask,
+                          float drop_scale, uint64_t drop_seed, float drop_p, const gi_bn_acc_args* b, const void* side_src, void* side_dst,
+                          int64_t side_bytes) {
+  GI_REQUIRE(ctx && x && y, "debug_bn_apply_acc: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && dbg_act_ok(act) && pixels >= 1, "debug_bn_apply_acc: dtype=%d act=%d pixels=%lld", dtype, act, (long long)pixels);
+  GI_REQUIRE(dbg_c_ok(dtype, c), "debug_bn_apply_acc: c=%d unsupported", c);
+  GI_REQUIRE(dbg_view_ok(dtype, c, ldy, coffy), "debug_bn_apply_acc: ldy=%d coffy=%d for %d channels", ldy, coffy, c);
+  GI_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || drop_mask), "debug_bn_apply_acc: drop_p=%g needs a mask to store the draw", (double)drop_p);
+  GI_REQUIRE(side_bytes >= 0, "debug_bn_apply_acc: side_bytes=%lld", (long long)side_bytes);
+  BnAccArgs o;
+  GI_TRY(dbg_bn_acc("debug_bn_apply_acc", c, b, o));
+  return op_bn_apply_acc(ctx->stream, dtype, x, y, pixels, c, ldy, coffy, act, drop_mask, drop_scale, drop_seed, drop_p, o, side_src, side_dst,
+                         side_bytes);
+}
+
+int gi_debug_act_bn_bwd(gi_ctx* ctx, int dtype, const gi_act_bn_bwd_args* s) {
+  GI_REQUIRE(ctx, "debug_act_bn_bwd: null context");
+  ActBnBwdArgs a;
+  GI_TRY(dbg_bwd_args("debug_act_bn_bwd", dtype, s, true, a));
+  GI_REQUIRE(a.groups == 1 || a.groups == 2, "debug_act_bn_bwd: groups=%d (1 or 2)", a.groups);
+  GI_REQUIRE(a.groups == 1 || a.stat_stride >= a.c, "debug_act_bn_bwd: stat_stride=%d below the %d channels", a.stat_stride, a.c);
+  GI_REQUIRE(!a.has_bn || (a.x && a.gamma && a.save_mean && a.save_invstd), "debug_act_bn_bwd: BatchNorm without x / gamma / save_mean / save_invstd");
+  GI_REQUIRE((a.fwd_scale == nullptr) == (a.fwd_shift == nullptr), "debug_act_bn_bwd: fwd_scale and fwd_shift go together");
+  const bool need_y = a.g2 != nullptr || a.act != GI_ACT_NONE;
+  GI_REQUIRE(!need_y || a.y || (a.has_bn && a.fwd_scale), "debug_act_bn_bwd: the activation's sign needs y or fwd_scale / fwd_shift");
+  GI_REQUIRE(!a.acc || (a.acc_reps >= 1 && a.acc_reps <= GI_STAT_MAXREP), "debug_act_bn_bwd: acc_reps=%d outside 1..%d", a.acc_reps, GI_STAT_MAXREP);
+  GI_REQUIRE(!a.reduce_done || (a.acc && a.has_bn && !a.eval_bn), "debug_act_bn_bwd: reduce_done needs train-mode accumulators");
+  GI_REQUIRE(!a.has_bn || a.acc || (a.partials && a.sums), "debug_act_bn_bwd: BatchNorm without accumulators needs partials and sums");
+  GI_REQUIRE(a.zero_words >= 0, "debug_act_bn_bwd: zero_words=%d", a.zero_words);
+  return op_act_bn_bwd(ctx->stream, dtype, a);
+}
+
+int gi_debug_in_forward(gi_ctx* ctx, int dtype, const void* x, void* y, int n, int hw, int c, int ldy, int coffy, int act,
+                        const uint8_t* drop_mask, float drop_scale, float eps, float* stats) {
+  GI_REQUIRE(ctx && x && y && stats, "debug_in_forward: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && dbg_act_ok(act), "debug_in_forward: dtype=%d act=%d", dtype, act);
+  GI_REQUIRE(c > 0 && c % dbg_epc(dtype) == 0 && dbg_view_ok(dtype, c, ldy, coffy), "debug_in_forward: c=%d ldy=%d coffy=%d", c, ldy, coffy);
+  return op_in_forward(ctx->stream, dtype, x, y, n, hw, c, ldy, coffy, act, drop_mask, drop_scale, eps, stats);
+}
+
+int gi_debug_act_in_bwd(gi_ctx* ctx, int dtype, const gi_act_bn_bwd_args* s, int n, int hw, const float* stats) {
+  GI_REQUIRE(ctx && stats, "debug_act_in_bwd: null pointer");
+  ActBnBwdArgs a;
+  GI_TRY(dbg_bwd_args("debug_act_in_bwd", dtype, s, false, a));
+  GI_REQUIRE(n >= 1 && hw >= 1, "debug_act_in_bwd: n=%d hw=%d", n, hw);
+  const bool need_y = a.g2 != nullptr || a.act != GI_ACT_NONE;
+  GI_REQUIRE(!need_y || a.y, "debug_act_in_bwd: the activation's sign needs y");
+  return op_act_in_bwd(ctx->stream, dtype, a, n, hw, stats);
+}
+
+int gi_debug_bias_grad(gi_ctx* ctx, int dtype, const void* dz, int64_t pixels, int c, float scale, float* dbias, float* partials) {
+  GI_REQUIRE(ctx && dz && dbias && partials, "debug_bias_grad: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && pixels >= 1, "debug_bias_grad: dtype=%d pixels=%lld", dtype, (long long)pixels);
+  return op_bias_grad(ctx->stream, dtype, dz, pixels, c, scale, dbias, partials);
+}
+
+int gi_debug_tanh_bwd(gi_ctx* ctx, const float* dy, const float* y, float* dx, int64_t count, float scale) {
+  GI_REQUIRE(ctx && dy && y && dx && count >= 0, "debug_tanh_bwd: bad argument");
+  return op_tanh_bwd(ctx->stream, dy, y, dx, count, scale);
+}
+
+int gi_debug_fill_dropout(gi_ctx* ctx, uint8_t* mask_nhwc, int64_t count, uint64_t seed, float p) {
+  GI_REQUIRE(ctx && mask_nhwc && count >= 0, "debug_fill_dropout: bad argument");
+  GI_REQUIRE(p >= 0.f && p < 1.f, "debug_fill_dropout: p=%g outside [0, 1)", (double)p);
+  return op_fill_dropout(ctx->stream, mask_nhwc, count, seed, p);
+}
+
+int gi_debug_mask_layout(gi_ctx* ctx, const uint8_t* src, uint8_t* dst, int n, int c, int hw, int to_nhwc) {
+  GI_REQUIRE(ctx && src && dst && src != dst, "debug_mask_layout: bad pointer");
+  GI_REQUIRE(n >= 1 && c >= 1 && hw >= 1, "debug_mask_layout: n=%d c=%d hw=%d", n, c, hw);
+  return op_mask_nchw_to_nhwc(ctx->stream, src, dst, n, c, hw, to_nhwc);
+}
+
+int gi_debug_mul_slope(gi_ctx* ctx, int dtype, const void* tin, const void* a, void* tout, int64_t count) {
+  GI_REQUIRE(ctx && tin && a && tout, "debug_mul_slope: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && count >= 0, "debug_mul_slope: dtype=%d count=%lld", dtype, (long long)count);
+  return op_mul_slope(ctx->stream, dtype, tin, a, tout, count);
+}
+
+int gi_debug_bn_tangent_inject(gi_ctx* ctx, int dtype, const void* dta, const void* y, const void* tx, const void* x, void* dxp, int64_t pixels,
+                               int c, const float* gamma, const float* mean, const float* inv, float* dgamma, float dgamma_scale, float* partials,
+                               float* sums) {
+  GI_REQUIRE(ctx && dta && y && tx && x && dxp && gamma && mean && inv && partials && sums, "debug_bn_tangent_inject: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype) && pixels >= 1, "debug_bn_tangent_inject: dtype=%d pixels=%lld", dtype, (long long)pixels);
+  return op_bn_tangent_inject(ctx->stream, dtype, dta, y, tx, x, dxp, pixels, c, gamma, mean, inv, dgamma, dgamma_scale, partials, sums);
+}
+
+int gi_debug_gp_direction(gi_ctx* ctx, const float* g, int n, int64_t hw, float lam, float* sumsq, float* amax, float* v, float* penalty,
+                          float* sc) {
+  GI_REQUIRE(ctx && g && sumsq && amax && v && sc, "debug_gp_direction: null pointer");
+  GI_REQUIRE(n >= 1 && hw >= 1, "debug_gp_direction: n=%d hw=%lld", n, (long long)hw);
+  return op_gp_direction(ctx->stream, g, n, hw, lam, sumsq, amax, v, penalty, sc);
+}
+
+int gi_debug_gp_unscale_add(gi_ctx* ctx, const float* src, const float* sc, float* dst, int64_t count) {
+  GI_REQUIRE(ctx && src && sc && dst && count >= 0, "debug_gp_unscale_add: bad argument");
+  return op_gp_unscale_add(ctx->stream, src, sc, dst, count);
+}
+
+int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends, int rows) {
+  GI_REQUIRE(ctx && acc && addends, "debug_stat_acc_add: null pointer");
+  GI_REQUIRE(c >= 1 && rows >= 1, "debug_stat_acc_add: c=%d rows=%d", c, rows);
+  GI_REQUIRE(reps >= 1 && reps <= GI_STAT_MAXREP, "debug_stat_acc_add: reps=%d outside 1..%d", reps, GI_STAT_MAXREP);
+  GI_REQUIRE((group == 0 || group == 1) && (q == 0 || q == 1), "debug_stat_acc_add: group=%d q=%d (0 or 1 each)", group, q);
+  hipLaunchKernelGGL(stat_acc_add_kernel, dim3(rows), dim3(256), 0, ctx->stream, acc, c, reps, group, q, addends);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase) {
   GI_REQUIRE(ctx && w, "pack_weights: null pointer");
   return op_pack_weights(ctx->stream, dtype, w, ca, cb, w_packed, w_phase);

@@ -40,7 +40,7 @@ __device__ __forceinline__ void bn_from_acc(const BnAccP& a, int c, int ch, int 
   gi_stat_read2<COHERENT>(a.acc, c, a.reps, j, ch, t0, t1);
   const double m = t0 / a.count;
   double v = t1 / a.count - m * m;
-  if (v < 0.0) v = 0.0;
+  if (v < 0.0 || a.count <= 1.0) v = 0.0;   // (one sample has no spread, whatever rounding its square carries)
   const float mean = (float)m, var = (float)v;
   const float inv = 1.0f / sqrtf(var + a.eps);
   const float sc = gam * inv;

@@ -86,7 +86,8 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* partials,
       if (train) {
         const double m = s / count;
         double v = q / count - m * m;
-        if (v < 0.0) v = 0.0;
+        // (one sample has no spread: the fp32 rounding of its square - up to 6e-8 x^2, next to eps = 1e-5 - is not a variance)
+        if (v < 0.0 || count <= 1.f) v = 0.0;
         mean = (float)m;
         var = (float)v;
         const float unbiased = count > 1.f ? (float)(v * (double)count / ((double)count - 1.0)) : var;
@@ -831,7 +832,7 @@ __global__ void __launch_bounds__(256) in_forward_kernel(const char* x, char* y,
     if (threadIdx.x == 0) {
       const double m = a / hw;
       double var = b / hw - m * m;
-      if (var < 0.0) var = 0.0;
+      if (var < 0.0 || hw == 1) var = 0.0;   // (one pixel has no spread: what is left is the fp32 rounding of its square)
       const float inv = 1.0f / sqrtf((float)var + eps);
       aff[e] = (float)m; aff[8 + e] = inv;
       stats[((int64_t)img * c + cc * EPC + e) * 2] = (float)m;

@@ -586,6 +586,96 @@ int gi_c1_head4_forward(gi_ctx* ctx, const void* X, const float* w, const float*
                         int Hs, int Ws, int ldx, int coffx, int relu_in, void* col_scratch);
 int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, int n, int Hs, int Ws, int ldout,
                       int coffout);
+/* ---- the normalisation and activation-backward passes on their own (test seam) ---------------------------------------------
+ * Each entry checks what the kernels assume and forwards to the pass of csrc/elementwise.hip that the networks call; nothing here is
+ * on a training path. Tensors are NHWC of the compute type T (pixels x channels, row pitch ld, channel offset coff; both multiples of
+ * the 16-byte chunk: 8 channels for fp16, 4 for fp32); vectors are fp32. c / chunk must be a power of two <= 256 except for the
+ * InstanceNorm passes (any multiple of the chunk). tests/norm_ref.py restates every one of them in fp64.
+ * col_stats: partials[row][2][c] = column sum / sum of squares of a dense (pixels, c) tensor, *rows_out rows
+ * (partials: at least (pixels / 32 + 8) * 2 * c floats).
+ * bn_finalize: BatchNorm2d from partial rows: scale = gamma * inv, shift = beta - mean * scale, save_mean, save_invstd; train: batch
+ * statistics (biased variance), running statistics moved with `momentum` (unbiased variance; count 1: the biased one); eval: the
+ * running statistics. groups = 2: two populations, their rows part_stride floats and their outputs out_stride floats apart, the
+ * running statistics moved population by population.
+ * bn_apply: y[p][coffy + ch] = drop(act(fma(x[p][ch], scale, shift))), drop = keep-mask byte (dense, pixels x c) ? v * drop_scale : 0.
+ * 0 < pg < pixels: pixels >= pg take scale / shift at + gstride floats. */
+int gi_debug_col_stats(gi_ctx* ctx, int dtype, const void* x, int64_t pixels, int c, float* partials, int* rows_out);
+int gi_debug_bn_finalize(gi_ctx* ctx, const float* partials, int rows, int c, int64_t count, const float* gamma,
+                         const float* beta, float* running_mean, float* running_var, float* scale, float* shift,
+                         float* save_mean, float* save_invstd, int train, float momentum, float eps, int groups,
+                         int64_t part_stride, int out_stride);
+int gi_debug_bn_apply(gi_ctx* ctx, int dtype, const void* x, void* y, int64_t pixels, int c, int ldy, int coffy,
+                      const float* scale, const float* shift, int act, const uint8_t* drop_mask, float drop_scale, int64_t pg,
+                      int gstride);
+/* The same from an exact accumulator block (csrc/stat_acc.h: quantity 0 = sum x, 1 = sum x^2 per population), train mode only. */
+typedef struct gi_bn_acc_args {
+  const unsigned long long* acc; int reps;       /* block of gi_stat_acc_words(c) words, `reps` replicas in use (1 .. 4) */
+  const float* gamma; const float* beta;
+  float* running_mean; float* running_var;
+  float* scale; float* shift; float* save_mean; float* save_invstd;   /* [groups], out_stride floats apart */
+  int64_t count;                                 /* pixels per population */
+  float momentum, eps;
+  int groups, out_stride;
+  unsigned long long* zero_next; int zero_words; /* optional: 64-bit words the pass clears */
+} gi_bn_acc_args;
+int gi_debug_bn_finalize_acc(gi_ctx* ctx, int c, const gi_bn_acc_args* b);
+/* finalize + bn_apply in one pass over pixels = groups * count. drop_mask with drop_p > 0: the keep-mask is drawn in the pass
+ * (gi_debug_fill_dropout's draw for drop_seed) and stored there; drop_p == 0: it is read. side_bytes > 0 (a multiple of 16): side_src
+ * is copied to side_dst by the same launch. */
+int gi_debug_bn_apply_acc(gi_ctx* ctx, int dtype, const void* x, void* y, int64_t pixels, int c, int ldy, int coffy, int act,
+                          uint8_t* drop_mask, float drop_scale, uint64_t drop_seed, float drop_p, const gi_bn_acc_args* b,
+                          const void* side_src, void* side_dst, int64_t side_bytes);
+/* backward through [dropout] -> activation -> [BatchNorm]: dz = (g1 + g2 * [s > 0]) * (s > 0 ? 1 : slope(act)) * drop_scale with
+ * s = y, or fma(x, fwd_scale, fwd_shift) when those are given; slope: 1 / 0 / 0.2 for none / ReLU / LeakyReLU. Without BatchNorm
+ * dx = dz. Train-mode BatchNorm: dx = gamma * inv * (dz - mean(dz) - xhat * mean(dz * xhat)) per population, dbeta += sum dz *
+ * inv_loss_scale, dgamma += sum dz * xhat * inv_loss_scale; eval_bn: dx = gamma * inv * dz, the parameter gradients untouched.
+ * drop_scale != 1 needs act = ReLU: the dropout zeros are taken from y > 0. */
+typedef struct gi_act_bn_bwd_args {
+  const void* g1; int ldg1, coffg1;              /* may be NULL */
+  const void* g2; int ldg2, coffg2;              /* may be NULL */
+  const void* y; int ldy, coffy;                 /* saved activation output */
+  const void* x;                                 /* raw tensor in front of the norm, dense; NULL without has_bn */
+  void* dx;                                      /* dense */
+  int64_t pixels; int c;
+  int act; float drop_scale;
+  int has_bn, eval_bn;
+  const float* gamma; const float* save_mean; const float* save_invstd;
+  float* dgamma; float* dbeta; float inv_loss_scale;
+  float* partials;                               /* scratch (pixels / 32 + 8) * 2 * c floats */
+  float* sums;                                   /* scratch groups * 8 * c floats */
+  const float* fwd_scale; const float* fwd_shift;
+  int groups, stat_stride;                       /* 2: two populations, the second one's vectors at + stat_stride floats */
+  unsigned long long* acc; int acc_reps;         /* exact accumulator block (zeroed) for the two sums, or NULL */
+  unsigned long long* zero_next; int zero_words;
+  int reduce_done;                               /* 1: the sums are in acc already */
+} gi_act_bn_bwd_args;
+int gi_debug_act_bn_bwd(gi_ctx* ctx, int dtype, const gi_act_bn_bwd_args* a);
+/* InstanceNorm2d(affine = False): statistics per (image, channel) over hw pixels, stats[n][c][2] = mean, inv; x dense (n * hw, c).
+ * The backward takes g1, g2, y, x, dx, pixels, c, act and drop_scale from the argument block. */
+int gi_debug_in_forward(gi_ctx* ctx, int dtype, const void* x, void* y, int n, int hw, int c, int ldy, int coffy, int act,
+                        const uint8_t* drop_mask, float drop_scale, float eps, float* stats);
+int gi_debug_act_in_bwd(gi_ctx* ctx, int dtype, const gi_act_bn_bwd_args* a, int n, int hw, const float* stats);
+/* dbias[ch] += scale * sum_p dz[p][ch] (partials: scratch as for col_stats); dx = dy * (1 - y^2) * scale; keep-mask bytes of the
+ * counter-based dropout draw (1 with probability 1 - p); byte masks between (n, c, hw) and (n, hw, c) */
+int gi_debug_bias_grad(gi_ctx* ctx, int dtype, const void* dz, int64_t pixels, int c, float scale, float* dbias, float* partials);
+int gi_debug_tanh_bwd(gi_ctx* ctx, const float* dy, const float* y, float* dx, int64_t count, float scale);
+int gi_debug_fill_dropout(gi_ctx* ctx, uint8_t* mask_nhwc, int64_t count, uint64_t seed, float p);
+int gi_debug_mask_layout(gi_ctx* ctx, const uint8_t* src, uint8_t* dst, int n, int c, int hw, int to_nhwc);
+/* gradient-penalty helpers: tout = tin * (a > 0 ? 1 : 0.2); the primal-gradient term of a differentiated BatchNorm tangent map
+ * (dxp += inj, dgamma += dgamma_scale * A * inv; partials: (pixels / 32 + 8) * 5 * c floats, sums: 5 * c floats); the penalty's
+ * direction v = s * d(lam * mean_n (||g_n|| - 1)^2) / dg with s = 2^k so that max|v| is in [1, 2), sc = {s, 1 / s}, sumsq / amax n
+ * floats each; dst += src * sc[1] */
+int gi_debug_mul_slope(gi_ctx* ctx, int dtype, const void* tin, const void* a, void* tout, int64_t count);
+int gi_debug_bn_tangent_inject(gi_ctx* ctx, int dtype, const void* dta, const void* y, const void* tx, const void* x, void* dxp,
+                               int64_t pixels, int c, const float* gamma, const float* mean, const float* inv, float* dgamma,
+                               float dgamma_scale, float* partials, float* sums);
+int gi_debug_gp_direction(gi_ctx* ctx, const float* g, int n, int64_t hw, float lam, float* sumsq, float* amax, float* v,
+                          float* penalty, float* sc);
+int gi_debug_gp_unscale_add(gi_ctx* ctx, const float* src, const float* sc, float* dst, int64_t count);
+/* adds addends[row][c] (fp32, device) to quantity q of population `group` of an accumulator block, row r into replica r & (reps - 1),
+ * one workgroup per row and one lane per channel as the producing kernels do */
+int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends,
+                          int rows);
 /* fp32 master [a][16][b] -> T [a][16*b] (w_packed) and T [4][b][4*a] (w_phase); either may be NULL */
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase);
 int gi_convert(gi_ctx* ctx, int dtype, const float* src, void* dst, int64_t count);      /* fp32 -> T */
