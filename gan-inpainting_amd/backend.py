@@ -47,6 +47,8 @@ PROTOTYPES = {
     "gi_net_set_loss_scale": (_i, [_vp, _f]),
     "gi_net_set_bn_groups": (_i, [_vp, _i]),
     "gi_net_set_dropout_seed": (_i, [_vp, _u64]),
+    "gi_net_get_dropout_state": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gi_net_set_dropout_state": (_i, [_vp, _u64, _u64]),
     "gi_net_dropout_mask": (_i, [_vp, _i, _i, _vp, _i64]),
     "gi_net_saved_activation": (_i, [_vp, _i, _i, _i, _vp, _i64]),
     "gi_net_debug_nonzero_tickets": (_i, [_vp, _vp]),
@@ -132,6 +134,7 @@ PROTOTYPES = {
     "gi_check_finite_scan_word": (_i, [_vp, _vp, _i64, _vp, _i]),
     "gi_adam_step_scan": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _f, _vp, _i, _i]),
     "gi_rmsprop_step_scan": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _vp, _i, _i]),
+    "gi_ema_update": (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
     "gi_wgrad_s2_scratch_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "gi_wgrad_s2_ws": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64]),
     "gi_c1_gather": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),

@@ -1312,15 +1312,59 @@ __global__ void __launch_bounds__(256) clamp_kernel(float* p, int64_t count, flo
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256)
     p[i] = fminf(fmaxf(p[i], lo), hi);
 }
-// grid (slices, nseg): out[s] += sum|g| over slice / len
-__global__ void __launch_bounds__(256) absmean_kernel(const float* g, const int64_t* off, const int64_t* len, float* out) {
+// Exponential moving average of a flat parameter buffer (optim.EMA): ema += om * (p - ema), om = 1 - decay. Two roundings per element,
+// both written out so that contraction cannot change them: diff = p - ema, then one fused multiply-add. guard (may be null): guard[1]
+// is the verdict the update's first optimizer kernel recorded (gi_guard_verdict); a skipped update leaves the average alone too.
+// 12 bytes per element and no reuse. Elements [head, head + 4 * n4) go as 16-byte chunks, two in flight per thread (the caller
+// passes n4 > 0 only when ema + head and p + head are both 16-byte aligned); the head and what follows the chunks go one by one.
+__device__ __forceinline__ float ema_one(float e, float q, float om) { return __fmaf_rn(om, __fsub_rn(q, e), e); }
+__global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t count, float om,
+                                                  const int* guard, int64_t head, int64_t n4) {
+  if (guard && guard[1] != 0) return;
+  const int64_t stride = (int64_t)gridDim.x * 256, tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  f4_t* e4 = (f4_t*)(ema + head);
+  const f4_t* p4 = (const f4_t*)(p + head);
+  int64_t i = tid;
+  for (; i + stride < n4; i += 2 * stride) {
+    f4_t a = e4[i], b = e4[i + stride];
+    const f4_t qa = p4[i], qb = p4[i + stride];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { a[k] = ema_one(a[k], qa[k], om); b[k] = ema_one(b[k], qb[k], om); }
+    e4[i] = a;
+    e4[i + stride] = b;
+  }
+  if (i < n4) {
+    f4_t a = e4[i];
+    const f4_t qa = p4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = ema_one(a[k], qa[k], om);
+    e4[i] = a;
+  }
+  const int64_t rest = count - 4 * n4;     // the head and the tail: fewer than 8 elements when the chunks cover the rest, else all
+  for (int64_t j = tid; j < rest; j += stride) {
+    const int64_t idx = j < head ? j : j + 4 * n4;
+    ema[idx] = ema_one(ema[idx], p[idx], om);
+  }
+}
+// grid (slices, nseg): partials[s][slice] = sum|g| over the slice's share of segment s; absmean_final_kernel adds a segment's
+// slices in slice order and divides by its length. No float atomics: the logged means do not depend on which workgroup ends
+// first, so a run's gradient-flow history is reproducible bit for bit like its weights.
+constexpr int kAbsmeanSlices = 32, kAbsmeanMaxSeg = 256;
+__global__ void __launch_bounds__(256) absmean_kernel(const float* g, const int64_t* off, const int64_t* len, double* partials) {
   __shared__ double sh[4];
   const int sgm = blockIdx.y;
   const int64_t o = off[sgm], l = len[sgm];
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < l; i += (int64_t)gridDim.x * 256) s += fabsf(g[o + i]);
   s = block_sum(s, sh);
-  if (threadIdx.x == 0 && s != 0.0) atomicAdd(out + sgm, (float)(s / (double)l));
+  if (threadIdx.x == 0) partials[sgm * gridDim.x + blockIdx.x] = s;
+}
+__global__ void __launch_bounds__(256) absmean_final_kernel(const double* partials, const int64_t* len, int nseg, int slices, float* out) {
+  const int sgm = blockIdx.x * 256 + threadIdx.x;
+  if (sgm >= nseg) return;
+  double s = 0.0;
+  for (int k = 0; k < slices; ++k) s += partials[sgm * slices + k];
+  out[sgm] = s != 0.0 ? (float)(s / (double)len[sgm]) : 0.f;
 }
 
 // ---- weight packing / conversion ---------------------------------------------------------------
@@ -1978,10 +2022,31 @@ int gi_clamp(gi_ctx* ctx, float* p, int64_t count, float lo, float hi) {
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
+int gi_ema_update(gi_ctx* ctx, float* ema, const float* p, int64_t count, float decay, const int* guard) {
+  GI_REQUIRE(ctx && ema && p && count > 0, "ema_update: null argument or count=%lld", (long long)count);
+  GI_REQUIRE(decay >= 0.f && decay <= 1.f, "ema_update: decay=%g outside [0, 1]", (double)decay);
+  const uintptr_t ae = reinterpret_cast<uintptr_t>(ema), ap = reinterpret_cast<uintptr_t>(p);
+  GI_REQUIRE((ae & 3) == 0 && (ap & 3) == 0, "ema_update: pointers must be 4-byte aligned");
+  // flat views start at any float offset: 16-byte chunks need both pointers to reach a 16-byte boundary after the same head
+  int64_t head = 0, n4 = 0;
+  if (((ae ^ ap) & 15) == 0) {
+    head = (int64_t)(((16 - (ae & 15)) & 15) / 4);
+    if (head > count) head = count;
+    n4 = (count - head) / 4;
+  }
+  const float om = 1.0f - decay;
+  // at most the 2048 workgroups that are resident at once (256 CUs x 8), 32 bytes of each buffer per thread and round
+  hipLaunchKernelGGL(ema_kernel, dim3(nblocks(n4 > 0 ? n4 : count, 2)), dim3(256), 0, ctx->stream, ema, p, count, om, guard, head, n4);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
 int gi_grad_absmean(gi_ctx* ctx, const float* g, const int64_t* seg_off, const int64_t* seg_len, int nseg, float* out) {
-  GI_REQUIRE(nseg > 0, "grad_absmean: nseg=%d", nseg);
-  GI_HIP(hipMemsetAsync(out, 0, sizeof(float) * nseg, ctx->stream));
-  hipLaunchKernelGGL(absmean_kernel, dim3(32, nseg), dim3(256), 0, ctx->stream, g, seg_off, seg_len, out);
+  GI_REQUIRE(ctx && nseg > 0 && nseg <= kAbsmeanMaxSeg, "grad_absmean: nseg=%d (1 .. %d)", nseg, kAbsmeanMaxSeg);
+  if (!ctx->absmean_partials) GI_HIP(hipMalloc((void**)&ctx->absmean_partials, sizeof(double) * kAbsmeanSlices * kAbsmeanMaxSeg));
+  hipLaunchKernelGGL(absmean_kernel, dim3(kAbsmeanSlices, nseg), dim3(256), 0, ctx->stream, g, seg_off, seg_len, ctx->absmean_partials);
+  GI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(absmean_final_kernel, dim3((nseg + 255) / 256), dim3(256), 0, ctx->stream, (const double*)ctx->absmean_partials, seg_len, nseg,
+                     kAbsmeanSlices, out);
   GI_LAUNCH_CHECK();
   return GI_OK;
 }

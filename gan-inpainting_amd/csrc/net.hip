@@ -670,6 +670,20 @@ extern "C" int gi_net_set_dropout_seed(gi_net* net, uint64_t seed) {
   net->drop_counter = 0;
   return GI_OK;
 }
+// The dropout stream is (seed, counter): every train-mode forward of a generator with dropout advances the counter by one. Reading
+// and writing both lets a resumed run draw the masks the uninterrupted run would have drawn.
+extern "C" int gi_net_get_dropout_state(gi_net* net, uint64_t* seed, uint64_t* counter) {
+  GI_REQUIRE(net && seed && counter, "get_dropout_state: null");
+  *seed = net->drop_seed;
+  *counter = net->drop_counter;
+  return GI_OK;
+}
+extern "C" int gi_net_set_dropout_state(gi_net* net, uint64_t seed, uint64_t counter) {
+  GI_REQUIRE(net, "set_dropout_state: null");
+  net->drop_seed = seed;
+  net->drop_counter = counter;
+  return GI_OK;
+}
 extern "C" int gi_net_dropout_mask(gi_net* net, int slot, int level, uint8_t* out_nchw, int64_t count) {
   GI_REQUIRE(net && net->kind == 0 && net->bound, "dropout_mask: generator handle required");
   GI_REQUIRE(slot >= 0 && slot < net->n_slots && level >= 5 && level <= net->nd - 1, "dropout_mask: slot=%d level=%d", slot, level);

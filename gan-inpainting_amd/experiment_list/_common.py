@@ -10,7 +10,9 @@ Differences to the reference, all host-side and listed in DESIGN.md:
     one copy per batch (util.GradFlow), accumulated on the device;
   * the evaluation pass (minimaxgan_l1.py:234-240) runs lib.models.evaluate.calculate_metric on the
     train and test loaders (reconstruction metrics on fused HIP reductions; FID when state['inception_model']
-    and state['train_fid'] / state['test_fid'] are set (train.py --fid-weights), else -1); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch).
+    and state['train_fid'] / state['test_fid'] are set (train.py --fid-weights), else -1); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch);
+  * opt-in (train.py --save-state / --resume / --ema-decay; none of it in the reference): the full training state in last_state.pt
+    at epoch boundaries, resuming from it, and an averaged generator evaluated and saved next to the live one.
 """
 import contextlib
 import logging
@@ -20,7 +22,7 @@ import time
 
 import torch
 
-from .. import optim, trainer
+from .. import checkpoint, optim, trainer
 from ..lib.models import evaluate, networks, util
 
 
@@ -131,9 +133,103 @@ def _fid_stats(state, mode):
     return (-1, -1) if st is None or isinstance(st, (int, float)) else st
 
 
-def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn, d_names, pass_extra=False, step=None):
+def _world():
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def make_ema(state, net_G):
+    """optim.EMA of the generator when --ema-decay > 0, else None. Call it after the step object is built: its constructor
+    broadcasts the parameters, so every replica's average starts from the same weights and needs no communication."""
+    decay = float(state.get("ema_decay") or 0.0)
+    return optim.EMA(net_G, decay) if decay > 0 else None
+
+
+def _rng_states(device):
+    return {"torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(device)}
+
+
+def _training_objects(net_G, nets_D, step):
+    nets = {"G": net_G}
+    nets.update({f"D{i}": d for i, d in enumerate(nets_D)})
+    opts = {f"opt{i}": o for i, o in enumerate(getattr(step, "_opts", ()))}
+    return nets, opts
+
+
+def _save_training_state(path, state, epoch, history, eval_hist, counters, loaders, device, net_G, nets_D, step, rank0):
+    """last_state.pt (rank 0) and this rank's RNG file. No collective: every rank reads its own objects."""
+    torch.cuda.synchronize(device)        # the side stream's optimizer and its guard flags included
+    rng = _rng_states(device)
+    checkpoint.save_state(checkpoint.rng_path(path, _rank()), {"format_version": checkpoint.FORMAT_VERSION, "rank": _rank(), **rng})
+    if not rank0:
+        return
+    nets, opts = _training_objects(net_G, nets_D, step)
+    ema = getattr(step, "ema_G", None)
+    payload = {
+        "format_version": checkpoint.FORMAT_VERSION, "title": state["title"],
+        "args": checkpoint.compat_args(state, _world(), nets), "epoch": int(epoch),
+        "history": history, "eval_hist": eval_hist, "counters": dict(counters or {}),
+        "nets": {k: {"state_dict": {n: v.detach().cpu().contiguous() for n, v in net.state_dict().items()},
+                     "training_state": net.training_state()} for k, net in nets.items()},
+        "optimizers": {k: o.state_dict() for k, o in opts.items()},
+        "step": step.state_dict() if step is not None else None,
+        "ema_G": ema.state_dict() if ema is not None else None,
+        "loaders": {k: l.state_dict() for k, l in loaders.items() if l is not None and hasattr(l, "state_dict")},
+        "rng": rng,
+    }
+    checkpoint.save_state(path, payload)
+
+
+def _load_training_state(path, state, logger, counters, loaders, device, net_G, nets_D, step):
+    """Restore everything _save_training_state wrote; returns (epoch, history, eval_hist). The RNG states go last: building
+    the loaders, the FID statistics and the networks all drew from the generators before this point."""
+    payload = checkpoint.load_state(path)
+    if payload["title"] != state["title"]:
+        raise checkpoint.CheckpointError(f"cannot resume: {path} was written by experiment {payload['title']!r}, this is {state['title']!r}")
+    nets, opts = _training_objects(net_G, nets_D, step)
+    checkpoint.check_compatible(payload["args"], checkpoint.compat_args(state, _world(), nets))
+    for k, net in nets.items():
+        net.load_state_dict(payload["nets"][k]["state_dict"])
+        ts = dict(payload["nets"][k]["training_state"])
+        if "dropout" in ts:    # the seed stays what the step constructor derived from the rank; the counter comes from the file
+            ts["dropout"] = {"seed": net.training_state()["dropout"]["seed"], "counter": ts["dropout"]["counter"]}
+        net.load_training_state(ts)
+    if set(payload["optimizers"]) != set(opts):
+        raise checkpoint.CheckpointError(f"cannot resume: the state holds optimizers {sorted(payload['optimizers'])}, this run {sorted(opts)}")
+    for k, o in opts.items():
+        o.load_state_dict(payload["optimizers"][k])
+    if step is not None and payload.get("step") is not None:
+        step.load_state_dict(payload["step"])
+    ema = getattr(step, "ema_G", None)
+    if (ema is None) != (payload.get("ema_G") is None):
+        raise checkpoint.CheckpointError("cannot resume: the state and this run disagree on whether the generator is averaged (ema_decay)")
+    if ema is not None:
+        ema.load_state_dict(payload["ema_G"])
+    for k, sd in payload.get("loaders", {}).items():
+        if loaders.get(k) is not None and hasattr(loaders[k], "load_state_dict"):
+            loaders[k].load_state_dict(sd)
+    if counters is not None:
+        counters.update(payload.get("counters", {}))
+    rng_file = checkpoint.rng_path(path, _rank())
+    rng = checkpoint.load_state(rng_file) if os.path.exists(rng_file) else payload["rng"]
+    if not os.path.exists(rng_file) and _rank() != 0:
+        raise checkpoint.CheckpointError(f"cannot resume: {rng_file} (this rank's RNG states) is missing")
+    torch.cuda.synchronize(device)
+    torch.set_rng_state(rng["torch"])
+    torch.cuda.set_rng_state(rng["cuda"], device)
+    logger.info("resumed from %s (epoch %d)", path, payload["epoch"])
+    return int(payload["epoch"]), payload["history"], payload["eval_hist"]
+
+
+def _g_state_dict(net_G):
+    return {k: v.detach().cpu().contiguous() for k, v in net_G.state_dict().items()}
+
+
+def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn, d_names, pass_extra=False, step=None, counters=None):
     """batch_fn(batch_index, ground, mask[, extra]) -> (loss dict of device scalars, g_updated: bool); extra = the
-    loader's third item (the segmentation labels of dataset.py:35-51) when pass_extra is set."""
+    loader's third item (the segmentation labels of dataset.py:35-51) when pass_extra is set.
+    counters: the plugin's dict of counters that outlive a batch (G_iter_count); saved and restored with the training state.
+    state['save_state'] / state['state_every'] / state['resume'] (train.py --save-state, --state-every, --resume): DESIGN.md."""
     num_epochs, save_every, evaluate_every = state["numepoch"], state["saveevery"], state["evalevery"]
     log_every = state.get("logevery", 50)
     gscale = step.sync.grad_scale() if (step is not None and getattr(step, "sync", None) is not None) else 1.0
@@ -143,11 +239,24 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
     side = step.side_stream() if step is not None else None
     side_keys = set(step.side_keys()) if step is not None else set()
     rank0 = _rank() == 0
+    ema = getattr(step, "ema_G", None)
+    state_every = int(state.get("state_every") or save_every)
+    state_path = os.path.join(exp_dir, checkpoint.STATE_FILE)
+    first_epoch = 0
+    resume = checkpoint.resolve(state.get("resume"), exp_dir)
+    if state.get("resume") and resume is None:
+        logger.info("--resume auto: no %s, starting fresh", state_path)
+    if resume is not None:
+        done, history, eval_hist = _load_training_state(resume, state, logger, counters, loaders, device, net_G, nets_D, step)
+        if done >= num_epochs:
+            logger.info("%s holds epoch %d, -ep is %d: nothing left to train", resume, done, num_epochs)
+            return history
+        first_epoch = done + 1
 
     def _on(stream):
         return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
-    for epoch in range(num_epochs + 1):
+    for epoch in range(first_epoch, num_epochs + 1):
         start = time.time()
         sums, g_updates, batches = {}, 0, 0
         acc_g = torch.zeros(len(flow_G.names), device=device)
@@ -200,6 +309,13 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                                                          inception_model=state.get("inception_model"), epoch=epoch,
                                                          prepare=eval_prepare(state, device, k, epoch))
                             for k in ("train", "test") if loaders.get(k) is not None}
+                if ema is not None:                              # the same metrics of the averaged generator
+                    with ema.applied():
+                        for k in ("train", "test"):
+                            if loaders.get(k) is not None:
+                                rec_eval[k + "_ema"] = evaluate.calculate_metric(
+                                    device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
+                                    inception_model=state.get("inception_model"), epoch=epoch, prepare=eval_prepare(state, device, k, epoch))
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))
             if rank0:        # every rank holds the same replica: one writer
@@ -209,8 +325,12 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                     pickle.dump(eval_hist, h, protocol=pickle.HIGHEST_PROTOCOL)
         if epoch % save_every == 0 and epoch > 0 and rank0:
             # same contract as the reference: G only, plain state_dict (minimaxgan_l1.py:253-255)
-            torch.save({k: v.detach().cpu().contiguous() for k, v in net_G.state_dict().items()},
-                       os.path.join(exp_dir, "epoch{}_G.pt".format(epoch)))
+            torch.save(_g_state_dict(net_G), os.path.join(exp_dir, "epoch{}_G.pt".format(epoch)))
+            if ema is not None:     # the averaged weights under the same keys (BatchNorm statistics: the live ones)
+                with ema.applied():
+                    torch.save(_g_state_dict(net_G), os.path.join(exp_dir, "epoch{}_G_ema.pt".format(epoch)))
+        if state.get("save_state") and epoch > 0 and epoch % state_every == 0:
+            _save_training_state(state_path, state, epoch, history, eval_hist, counters, loaders, device, net_G, nets_D, step, rank0)
         logger.info("epoch: %d, time: %.3fs, %s", epoch, time.time() - start,
                     ", ".join(f"{k}: {v:.6f}" for k, v in rec.items()))
     return history
@@ -242,4 +362,4 @@ def make_sync():
     return None
 
 
-__all__ = ["setup", "build_networks", "run_epochs", "make_optimizers", "make_sync", "wgan_cadence", "trainer"]
+__all__ = ["setup", "build_networks", "run_epochs", "make_optimizers", "make_sync", "make_ema", "wgan_cadence", "trainer"]

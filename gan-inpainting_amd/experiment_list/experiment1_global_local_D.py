@@ -15,6 +15,7 @@ def begin(state, loaders):
     opt_G, opt_D = C.make_optimizers("adam", net_G, optim.chain(net_Dl.parameters(), net_Dg.parameters()))   # :122-123
     step = C.trainer.DualDStep(net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=state.get("lambda1", 300.0),
                                lam2=state.get("lambda2", 300.0), sync=C.make_sync())
+    step.ema_G = C.make_ema(state, net_G)
 
     with_ssim = bool(state.get("ssim", True))
 

@@ -9,6 +9,7 @@ def begin(state, loaders):
     net_G, (net_D,) = C.build_networks(state, device, n_disc=1, sigmoid=True)
     opt_G, opt_D = C.make_optimizers("adam", net_G, net_D.parameters())
     step = C.trainer.MinimaxStep(net_G, net_D, opt_G, opt_D, recon="rmse", sync=C.make_sync())
+    step.ema_G = C.make_ema(state, net_G)
 
     def batch(bi, ground, mask):
         return step(ground, mask), True

@@ -12,6 +12,7 @@ def begin(state, loaders):
     opt_G, opt_D = C.make_optimizers("rmsprop", net_G, net_D.parameters())
     step = C.trainer.WGANStep(net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=C.make_sync(),
                               gp_lambda=float(state.get("gp_lambda", 0.0)), overlap=bool(state.get("overlap", True)))   # > 0: WGAN-GP extension instead of clipping
+    step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 
     def batch(bi, ground, mask):
@@ -21,4 +22,4 @@ def begin(state, loaders):
             counters["G_iter_count"] += 1
         return L, upd
 
-    return C.run_epochs(state, loaders, exp_dir, logger, device, net_G, [net_D], batch, ["avg_d"], step=step)
+    return C.run_epochs(state, loaders, exp_dir, logger, device, net_G, [net_D], batch, ["avg_d"], step=step, counters=counters)

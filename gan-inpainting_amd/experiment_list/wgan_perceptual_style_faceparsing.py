@@ -38,6 +38,7 @@ def begin(state, loaders):
     pgrad = pgrad and vgg is not None
     step = C.trainer.WGANPerceptualStep(net_G, net_D, opt_G, opt_D, vgg=vgg, segment_model=seg, clip=0.01, sync=C.make_sync(),
                                         overlap=bool(state.get("overlap", True)), perceptual_grad=pgrad)
+    step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 
     def batch(bi, ground, mask, segment):
@@ -47,4 +48,4 @@ def begin(state, loaders):
             counters["G_iter_count"] += 1
         return L, upd
 
-    return C.run_epochs(state, loaders, exp_dir, logger, device, net_G, [net_D], batch, ["avg_d"], pass_extra=True, step=step)
+    return C.run_epochs(state, loaders, exp_dir, logger, device, net_G, [net_D], batch, ["avg_d"], pass_extra=True, step=step, counters=counters)

@@ -191,6 +191,13 @@ class DeviceCachedLoader:
     def __len__(self):
         return len(self.cache) // self.batch_size
 
+    def state_dict(self):
+        """(seed, passes): what the order of every later pass follows from (resumable training)."""
+        return {"seed": int(self.seed), "passes": int(self.passes)}
+
+    def load_state_dict(self, sd):
+        self.seed, self.passes = int(sd["seed"]), int(sd["passes"])
+
     def __iter__(self):
         return self._batches(None)
 

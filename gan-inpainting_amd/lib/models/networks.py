@@ -252,6 +252,13 @@ class HipNet(nn.Module):
         if self._handle is not None:
             B.check(B.lib().gi_net_set_loss_scale(self._handle, self._loss_scale))
 
+    def training_state(self):
+        """What a training step reads from this object besides state_dict(): the fp16 loss scale (resumable training)."""
+        return {"loss_scale": float(self._loss_scale)}
+
+    def load_training_state(self, d):
+        self.set_loss_scale(d["loss_scale"])
+
     def zero_grad(self, set_to_none=False):
         if self._flat["grads"] is not None:
             self._flat["grads"].zero_()
@@ -468,6 +475,9 @@ class UnetGenerator(HipNet):
                                               max_n, self._dtype, self.n_slots, C.byref(h)))
         if getattr(self, "_drop_seed", None) is not None:      # a seed chosen before the handle existed
             B.check(B.lib().gi_net_set_dropout_seed(h, self._drop_seed))
+        if getattr(self, "_drop_state", None) is not None:     # ... and a loaded (seed, counter): for the first handle only
+            B.check(B.lib().gi_net_set_dropout_state(h, *self._drop_state))
+            self._drop_state = None
         return h
 
     def _output_shape(self, n, H, W):
@@ -476,8 +486,35 @@ class UnetGenerator(HipNet):
     # dropout control (parity tests feed the device-generated masks to the oracle, or impose masks)
     def set_dropout_seed(self, seed):
         self._drop_seed = int(seed)
+        self._drop_state = None
         if self._handle is not None:
             B.check(B.lib().gi_net_set_dropout_seed(self._handle, self._drop_seed))
+
+    _DEFAULT_DROP_SEED = 0x5EED0000     # the seed of a handle nobody seeded (gi_net in csrc/net.hip)
+
+    def training_state(self):
+        """HipNet's, plus the dropout stream (seed, counter): every train-mode forward that draws masks advances the counter."""
+        d = super().training_state()
+        if self._handle is not None:
+            seed, counter = C.c_uint64(), C.c_uint64()
+            B.check(B.lib().gi_net_get_dropout_state(self._handle, C.byref(seed), C.byref(counter)))
+            seed, counter = seed.value, counter.value
+        elif getattr(self, "_drop_state", None) is not None:
+            seed, counter = self._drop_state
+        else:
+            seed = self._drop_seed if getattr(self, "_drop_seed", None) is not None else self._DEFAULT_DROP_SEED
+            counter = 0
+        d["dropout"] = {"seed": int(seed), "counter": int(counter)}
+        return d
+
+    def load_training_state(self, d):
+        super().load_training_state(d)
+        if "dropout" in d:
+            seed, counter = int(d["dropout"]["seed"]), int(d["dropout"]["counter"])
+            if self._handle is not None:
+                B.check(B.lib().gi_net_set_dropout_state(self._handle, seed, counter))
+            else:
+                self._drop_state = (seed, counter)     # handles are created lazily: applied in _create_handle
 
     def dropout_masks(self, slot=None):
         """{level: uint8 keep-mask (N,C,H,W)} used by the last train-mode forward."""

@@ -2,6 +2,7 @@
     optim.Adam(net.parameters(), lr=0.0002, betas=(0.5, 0.999))     minimaxgan_l1.py:64-65
     optim.RMSprop(net.parameters(), lr=0.00005)                     wgan_l1.py:64-65
 One kernel per network over its flat fp32 parameter / gradient / state buffers."""
+import contextlib
 import itertools
 
 import torch
@@ -64,12 +65,58 @@ class _FlatOptimizer:
         for n in self.nets:
             n.zero_grad()
 
+    # ---- resumable training: everything an update reads besides the parameters and the gradients ----
+    kind = None
+    _moments = ()          # names of the per-network flat state tensors
+    _hyper = ()            # attribute names of the hyper-parameters
+
+    def _counts(self):
+        """Per network [parameter count, floats of the flat buffer]: the flat buffer pads every tensor to 64 floats, so two
+        networks of different shapes can share its length."""
+        return [[int(sum(p.numel() for p in n.parameters())), int(n.flat_params().numel())] for n in self.nets]
+
+    def state_dict(self):
+        """CPU copy of the optimizer: per network the flat moment tensors, the hyper-parameters, and the overflow guard (its four
+        device ints, the scan word of the last update, the skipped updates already polled). One device read-back."""
+        guard = None
+        if self._flags is not None:
+            guard = dict(flags=self._flags.detach().cpu().clone(), word=int(self._word), seen=int(self._seen))
+        return dict(kind=self.kind, hyper={k: getattr(self, k) for k in self._hyper},
+                    counts=self._counts(),
+                    state=[{k: st[k].detach().cpu().clone() for k in self._moments} for st in self.state], guard=guard)
+
+    def load_state_dict(self, sd):
+        if sd.get("kind") != self.kind:
+            raise B.BackendError(f"optimizer state of kind {sd.get('kind')!r} loaded into {self.kind!r}")
+        mine = self._counts()
+        if [list(c) for c in sd["counts"]] != mine:
+            raise B.BackendError(f"optimizer state holds networks of {[list(c) for c in sd['counts']]} [parameters, flat floats], "
+                                 f"this optimizer updates {mine}")
+        for i, (st, src) in enumerate(zip(self.state, sd["state"])):
+            for k in self._moments:
+                if k not in src or src[k].numel() != st[k].numel():
+                    raise B.BackendError(f"optimizer state of network {i}: tensor {k!r} has "
+                                         f"{src[k].numel() if k in src else 'no'} elements, expected {st[k].numel()}")
+                st[k].copy_(src[k].to(torch.float32).view_as(st[k]))
+        for k in self._hyper:
+            setattr(self, k, sd["hyper"][k])
+        if sd.get("guard") is None:
+            self._flags, self._seen = None, 0
+        else:
+            g = sd["guard"]
+            if g["flags"].numel() != 4:
+                raise B.BackendError(f"optimizer state: the overflow guard holds {g['flags'].numel()} ints, expected 4")
+            self._flags = g["flags"].to(torch.int32).to(self.nets[0].flat_params().device)
+            self._word, self._seen = int(g["word"]), int(g["seen"])
+
     def _done(self):
         for n in self.nets:
             n.mark_dirty()
 
 
 class Adam(_FlatOptimizer):
+    kind, _moments, _hyper = "adam", ("m", "v"), ("lr", "betas", "eps", "t")
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params)
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -99,6 +146,7 @@ class Adam(_FlatOptimizer):
 class RMSprop(_FlatOptimizer):
     """torch.optim.RMSprop defaults (alpha=0.99, eps=1e-8, no momentum, not centered). `clamp` > 0
     fuses the WGAN weight clipping p.data.clamp_(-clamp, clamp) into the same pass."""
+    kind, _moments, _hyper = "rmsprop", ("sq",), ("lr", "alpha", "eps", "clamp")
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, clamp=0.0):
         super().__init__(params)
@@ -114,6 +162,62 @@ class RMSprop(_FlatOptimizer):
             B.check(lib.gi_rmsprop_step_scan(B.get_ctx(p.device), B.ptr(p), B.ptr(g), B.ptr(st["sq"]), p.numel(), self.lr,
                                              self.alpha, self.eps, self.clamp, self.grad_scale, guard, word, 1 if k == 0 else 0))
         self._done()
+
+
+class EMA:
+    """Exponential moving average of a network's parameters: a flat fp32 copy of net.flat_params(), taken here, that update()
+    moves towards the live parameters by (1 - decay) in one HIP pass (gi_ema_update). BatchNorm running statistics are not
+    averaged: the averaged network runs with the live ones."""
+
+    def __init__(self, net, decay):
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"EMA decay {decay!r} outside [0, 1]")
+        p = net.flat_params()
+        if not p.is_cuda:
+            raise B.BackendError("EMA needs a network on a gfx950 device (move it with .to('cuda') first)")
+        self.net, self.decay = net, float(decay)
+        self.flat = p.detach().clone()
+
+    @torch.no_grad()
+    def update(self, opt=None):
+        """Call right after opt.step() on the same stream. With `opt`'s overflow guard on, an update the optimizer skipped is
+        skipped here as well (the verdict its first kernel recorded); no host synchronisation."""
+        p = self.net.flat_params()
+        guard = opt._flags if (opt is not None and opt.guard and opt._flags is not None) else None
+        B.check(B.lib().gi_ema_update(B.get_ctx(p.device), B.ptr(self.flat), B.ptr(p), p.numel(), self.decay, B.ptr(guard)))
+
+    def state_dict(self):
+        return dict(decay=self.decay, flat=self.flat.detach().cpu().clone())
+
+    def load_state_dict(self, sd):
+        if sd["flat"].numel() != self.flat.numel():
+            raise B.BackendError(f"EMA state holds {sd['flat'].numel()} parameters, the network has {self.flat.numel()}")
+        if float(sd["decay"]) != self.decay:
+            raise B.BackendError(f"EMA state was averaged with decay {sd['decay']!r}, this one uses {self.decay!r}")
+        self.flat.copy_(sd["flat"].to(torch.float32).view_as(self.flat))
+
+    @contextlib.contextmanager
+    def applied(self):
+        """The averaged weights in the live network for the duration of the block; the raw ones come back bit for bit. The two
+        flat buffers swap contents (through one temporary copy), and the network is marked dirty both times so that its
+        packed weight copies follow."""
+        p = self.net.flat_params()
+        with torch.no_grad():
+            raw = p.detach().clone()
+            p.copy_(self.flat)
+            self.flat.copy_(raw)
+            del raw
+        self.net.mark_dirty()
+        try:
+            yield self.net
+        finally:
+            p = self.net.flat_params()
+            with torch.no_grad():
+                avg = p.detach().clone()
+                p.copy_(self.flat)
+                self.flat.copy_(avg)
+                del avg
+            self.net.mark_dirty()
 
 
 def chain(*its):

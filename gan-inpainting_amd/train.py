@@ -92,6 +92,12 @@ class _Parser(argparse.ArgumentParser):
             self.error("--flip needs --cache device (the flips happen where the cached batches are assembled)")
         if a.cache_budget_gb is not None and a.cache_budget_gb <= 0:
             self.error("--cache-budget-gb must be positive")
+        if a.state_every is not None and a.state_every <= 0:
+            self.error("--state-every must be > 0")
+        if not 0.0 <= a.ema_decay < 1.0:
+            self.error("--ema-decay takes 0 <= D < 1 (0 = off)")
+        if a.resume not in ("", "auto") and len(a.experiments) > 1:
+            self.error("--resume PATH names one experiment's state: give one -exp, or --resume auto")
         return a
 
 
@@ -143,6 +149,19 @@ def build_parser():
                              "This DEPARTS from the reference, which evaluates both under no_grad (they are logged constants there). "
                              "Only the random stand-in feature network has been run: the fp16 range of the published weights' "
                              "activations and gradients is unchecked")
+    parser.add_argument("--save-state", dest="save_state", action="store_true", default=False,
+                        help="write <outdir>/model/<title>/last_state.pt at epoch boundaries: networks, optimizers, loss scales, "
+                             "dropout and RNG streams, histories - everything --resume needs to continue the run bit for bit")
+    parser.add_argument("--state-every", dest="state_every", type=int, default=None,
+                        help="epochs between two writes of last_state.pt (default: --saveevery)")
+    parser.add_argument("--resume", default="", metavar="PATH|auto",
+                        help="continue from a state written by --save-state. auto: <outdir>/model/<title>/last_state.pt when it exists, "
+                             "a fresh start when it does not, so the same command line can be submitted again and again. The resumed "
+                             "run equals the uninterrupted one bit for bit; -ep, --saveevery, --evalevery, --outdir, --workers and "
+                             "--cache may differ, but changing --cache changes the batch order and ends that promise")
+    parser.add_argument("--ema-decay", dest="ema_decay", type=float, default=0.0,
+                        help="> 0: keep an exponential moving average of the generator's weights (one HIP pass per generator update); "
+                             "the evaluation pass adds train_ema / test_ema and epoch<N>_G_ema.pt is saved next to epoch<N>_G.pt")
     return parser
 
 

@@ -90,8 +90,12 @@ class _StepBase:
     recon_weight = 1.0      # largest multiplier on a mean-reduced reconstruction loss (lambda)
     auto_loss_scale = True  # fp16 only: pick per-network loss scales from the batch geometry
 
-    def __init__(self, net_G, nets_D, device, sync=None):
+    def __init__(self, net_G, nets_D, device, sync=None, ema_G=None):
         self.G, self.Ds = net_G, list(nets_D)
+        # optim.EMA of the generator (or None): updated right after every generator update, on its stream. It may also be set
+        # after construction, which under data parallelism is after the parameter broadcast below
+        self.ema_G = ema_G
+        self._loaded_scales = self._loaded_L = None
         self.ops = _Ops(device)
         self.sync = sync
         self._shape = None
@@ -124,6 +128,7 @@ class _StepBase:
             self.L = {}
             if self.auto_loss_scale:
                 self._pick_loss_scales(ground)
+            self._apply_loaded_state()
 
     def _pick_loss_scales(self, ground):
         """fp16 backward: the gradient entering the generator is ~ lambda / (N*H*W) per pixel (mean-
@@ -138,6 +143,55 @@ class _StepBase:
         for d in self.Ds:
             if d._dtype == B.GI_F16:
                 d.set_loss_scale(min(65536.0, 64.0 * n))
+
+    # ---- resumable training ----
+    def _nets(self):
+        return [self.G] + self.Ds
+
+    def state_dict(self):
+        """What the step carries across batches and a result depends on: the networks' loss scales (poll_overflow halves them);
+        the loss scalars (a WGAN step returns the generator's terms of its LAST generator update on every batch, and the epoch
+        loop averages what it is handed: the first batches of an epoch see the previous epoch's values); plus whatever a
+        subclass adds in _extra_state. Reads the device: call it with the step's streams idle."""
+        return {"loss_scales": [float(n._loss_scale) for n in self._nets()],
+                "losses": {k: v.detach().float().cpu().clone() for k, v in getattr(self, "L", {}).items()},
+                "extra": self._extra_state()}
+
+    def load_state_dict(self, sd):
+        if len(sd["loss_scales"]) != len(self._nets()):
+            raise B.BackendError(f"step state holds {len(sd['loss_scales'])} loss scales, this step has {len(self._nets())} networks")
+        # kept until the first batch: _buffers picks the scales from the batch geometry there, and the loaded ones must survive it
+        self._loaded_scales = [float(v) for v in sd["loss_scales"]]
+        for n, v in zip(self._nets(), self._loaded_scales):
+            n.set_loss_scale(v)
+        self._loaded_L = dict(sd.get("losses") or {})
+        self._shape = None              # the next batch goes through _buffers, which applies both
+        self._load_extra_state(sd.get("extra") or {})
+
+    def _apply_loaded_state(self):
+        """First batch after load_state_dict, from _buffers: the loaded loss scales over the ones just picked, the loaded loss
+        scalars into the fresh dict."""
+        if self._loaded_scales is not None:
+            for n, v in zip(self._nets(), self._loaded_scales):
+                n.set_loss_scale(v)
+            self._loaded_scales = None
+        if self._loaded_L:
+            for k, v in self._loaded_L.items():
+                self.L[k] = v.to(self.ops.dev, torch.float32).view(1).clone()
+            torch.cuda.synchronize(self.ops.dev)     # once per resume: the side stream writes these too
+        self._loaded_L = None
+
+    def _extra_state(self):
+        return {}
+
+    def _load_extra_state(self, d):
+        pass
+
+    def _step_G(self, opt):
+        """_step of the generator's optimizer, then the moving average of its parameters (same stream, no synchronisation)."""
+        self._step(opt)
+        if self.ema_G is not None:
+            self.ema_G.update(opt)
 
     # ---- stream contract for readers of the step's results (plugins: loss accumulation, gradient-flow statistics) ----
     def side_stream(self):
@@ -259,8 +313,8 @@ class _StepBase:
 
 
 class MinimaxStep(_StepBase):
-    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True):
-        super().__init__(net_G, [net_D], net_G.device, sync)
+    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True, ema_G=None):
+        super().__init__(net_G, [net_D], net_G.device, sync, ema_G)
         self.D, self.optG, self.optD, self.recon = net_D, opt_G, opt_D, recon
         self.stacked = stacked      # D(ground) | D(inpainted) as one batch with per-half BatchNorm (see _d_pair)
         self._bind_optimizers(opt_G, opt_D)
@@ -294,7 +348,7 @@ class MinimaxStep(_StepBase):
         o.add(d_adv, self.g_rec, self.tmp1)
         o.mul(self.tmp1, self.mask_c, self.g_gen)                              # d(inpainted)/d(gen) = mask
         self._bwd_G(gtok, self.g_gen)
-        self._step(self.optG)
+        self._step_G(self.optG)
         return self.L
 
 
@@ -302,8 +356,9 @@ class WGANStep(_StepBase):
     """clip > 0 applies the reference's weight clipping after the critic update. If opt_D is this
     package's RMSprop its `clamp` is set so the clip is fused into the optimizer kernel."""
 
-    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=None, gp_lambda=0.0, overlap=False, stacked=True):
-        super().__init__(net_G, [net_D], net_G.device, sync)
+    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=None, gp_lambda=0.0, overlap=False, stacked=True,
+                 ema_G=None):
+        super().__init__(net_G, [net_D], net_G.device, sync, ema_G)
         self.D, self.optG, self.optD, self.recon, self.clip = net_D, opt_G, opt_D, recon, clip
         # stacked=True: the critic's two calls of a batch, D(ground) and D(inpainted) (wgan_l1.py:134-135), run as ONE
         # 2n batch with independent BatchNorm statistics per half (gi_net_set_bn_groups): same arithmetic per
@@ -397,7 +452,7 @@ class WGANStep(_StepBase):
             o.add(d_adv, g_other, self.tmp1)
             o.mul(self.tmp1, self.mask_c, self.g_gen)
             self._bwd_G(gtok, self.g_gen)
-            self._step(self.optG)
+            self._step_G(self.optG)
         return self.L
 
     def side_stream(self):
@@ -445,7 +500,7 @@ class WGANStep(_StepBase):
             o.add(d_adv, self._g_losses(self.inpainted, ground), self.tmp1)
             o.mul(self.tmp1, self.mask_c, self.g_gen)
             self._bwd_G(gtok, self.g_gen)
-            self._step(self.optG)
+            self._step_G(self.optG)
         return self.L
 
     def _critic_stacked(self, ground, inp, x2=None, real_done=False):
@@ -494,6 +549,16 @@ class WGANPerceptualStep(WGANStep):
             self._ce2 = torch.zeros(2, dtype=torch.float32, device=net_G.device)
             self._zero1 = torch.zeros(1, dtype=torch.float32, device=net_G.device)
             self._dseg = None
+
+    def _extra_state(self):
+        # perceptual_grad on an fp16 generator: the loss scale was picked once from the first generator update's VGG gradient
+        return {"recon_weight": float(self.recon_weight),
+                "vgg_scaled_for": None if self._vgg_scaled_for is None else list(self._vgg_scaled_for)}
+
+    def _load_extra_state(self, d):
+        if "recon_weight" in d:
+            self.recon_weight = float(d["recon_weight"])
+            self._vgg_scaled_for = None if d.get("vgg_scaled_for") is None else tuple(d["vgg_scaled_for"])
 
     def __call__(self, ground, mask, update_g, segment=None):
         self.segment = segment
@@ -546,8 +611,8 @@ class DualDStep(_StepBase):
     """G step first, LSGAN losses, global + local (mask * x) discriminators, mask not ceil-ed,
     output not composited, one optimizer over both discriminators (:123)."""
 
-    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True):
-        super().__init__(net_G, [net_Dg, net_Dl], net_G.device, sync)
+    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True, ema_G=None):
+        super().__init__(net_G, [net_Dg, net_Dl], net_G.device, sync, ema_G)
         self.stacked = stacked      # each discriminator's real | fake calls as one batch with per-half BatchNorm
         self.Dg, self.Dl, self.optG, self.optD, self.lam1, self.lam2 = net_Dg, net_Dl, opt_G, opt_D, lam1, lam2
         self.recon_weight = max(lam1, lam2)
@@ -578,7 +643,7 @@ class DualDStep(_StepBase):
         o.mul(self.g_rec, mask, self.tmp1)
         o.add(self.g_adv, self.tmp1, self.g_gen)
         self._bwd_G(gtok, self.g_gen)
-        self._step(self.optG)                                                        # :172
+        self._step_G(self.optG)                                                        # :172
         # ---- D step :178-200
         self.optD.zero_grad()
         for net, real, fake, tag in ((self.Dg, ground, gen, "global"), (self.Dl, self.tmp2, self.inpainted, "local")):

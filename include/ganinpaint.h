@@ -168,7 +168,11 @@ int gi_net_set_loss_scale(gi_net* net, float scale);
  * groups with INDEPENDENT BatchNorm batch statistics (running statistics updated group by group). groups = 2 runs
  * the reference's two critic calls D(ground), D(inpainted) (wgan_l1.py:134-135) as one stacked batch. */
 int gi_net_set_bn_groups(gi_net* net, int groups);   /* fp16 backward scaling, default 65536 */
-int gi_net_set_dropout_seed(gi_net* net, uint64_t seed);
+int gi_net_set_dropout_seed(gi_net* net, uint64_t seed);   /* also resets the counter to 0 */
+/* the dropout stream is (seed, counter): each train-mode forward that draws masks advances the counter by one.
+ * Saved and restored by resumable training, so that a resumed run draws the masks of the uninterrupted one. */
+int gi_net_get_dropout_state(gi_net* net, uint64_t* seed, uint64_t* counter);
+int gi_net_set_dropout_state(gi_net* net, uint64_t seed, uint64_t counter);
 /* keep-mask of dropout level `level` used by the last train-mode forward of `slot`,
  * as uint8 in (N,C,H,W) order (what the oracle consumes); count = N*C*H*W */
 int gi_net_dropout_mask(gi_net* net, int slot, int level, uint8_t* out_nchw, int64_t count);
@@ -304,6 +308,11 @@ int gi_adam_step_scan(gi_ctx* ctx, float* p, const float* g, float* m, float* v,
                       float eps, int step, int skipped_seen, float grad_scale, int* guard, int word, int finish);
 int gi_rmsprop_step_scan(gi_ctx* ctx, float* p, const float* g, float* sq, int64_t count, float lr, float alpha, float eps,
                          float clamp, float grad_scale, int* guard, int word, int finish);
+/* exponential moving average of a flat parameter buffer, one launch on the context's stream (optim.EMA):
+ *   om = 1.0f - decay (fp32, on the host); per element diff = p - ema (rounded to fp32), ema = fmaf(om, diff, ema).
+ * 0 <= decay <= 1. guard (may be NULL): the flag4 of the optimizer that just updated p; when guard[1] != 0 - that update
+ * was skipped - ema is left untouched. ema and p may start at any float offset (16-byte accesses where both allow them). */
+int gi_ema_update(gi_ctx* ctx, float* ema, const float* p, int64_t count, float decay, const int* guard);
 /* mean(|g|) of `nseg` segments [off[i], off[i]+len[i]) of g -> out[i]
  * (gradient-flow statistics, minimaxgan_l1.py:180-182); offsets/lengths are device int64 */
 int gi_grad_absmean(gi_ctx* ctx, const float* g, const int64_t* seg_off, const int64_t* seg_len,
