@@ -169,6 +169,15 @@ PROTOTYPES = {
     "gi_debug_gp_direction": (_i, [_vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
     "gi_debug_gp_unscale_add": (_i, [_vp, _vp, _vp, _vp, _i64]),
     "gi_debug_stat_acc_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
+    "gi_debug_vgg_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "gi_debug_vgg_conv1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gi_debug_vgg_maxpool2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "gi_debug_vgg_tap_ws_bytes": (_i64, []),
+    "gi_debug_vgg_tap_terms": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, C.POINTER(_i)]),
+    "gi_debug_vgg_seed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f]),
+    "gi_debug_vgg_scale": (_i, [_vp, _vp, _vp]),
+    "gi_debug_vgg_act_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "gi_debug_vgg_conv1_adjoint": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i]),
     "gi_pack_weights": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
     "gi_convert": (_i, [_vp, _i, _vp, _vp, _i64]),
     "gi_convert_back": (_i, [_vp, _i, _vp, _vp, _i64]),

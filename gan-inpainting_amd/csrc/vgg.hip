@@ -643,6 +643,136 @@ int nblk(int64_t work, int per, int cap) {
   return (int)b;
 }
 
+// ---- host launch code: one copy of every grid rule, shared by the network runners below and the gi_debug_vgg_* entries --------------
+
+// fp32 master weights -> what the mode-2 kernels read: [cout][tap][cin], or (transposed) [cin][8 - tap][cout]
+int pack3x3(hipStream_t st, bool transposed, const float* w, half_t* out, int cout, int cin) {
+  const dim3 grid(nblk((int64_t)cout * 9 * cin, 256, 2048));
+  if (transposed) hipLaunchKernelGGL(pack3x3_t_kernel, grid, dim3(256), 0, st, w, out, cout, cin);
+  else hipLaunchKernelGGL(pack3x3_kernel, grid, dim3(256), 0, st, w, out, cout, cin);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int sum_cin(hipStream_t st, const float* w, float* w1) {
+  hipLaunchKernelGGL(sum_cin_kernel, dim3(3), dim3(256), 0, st, w, w1, 64, 3);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of the callers)
+int conv1(hipStream_t st, const float* xa, const float* xb, int n, int H, int W, const float* w1, const float* bias, half_t* out) {
+  hipLaunchKernelGGL(vgg_conv1_mfma_kernel, dim3(nblk((int64_t)2 * n * H * (W / 16), 4, 256 * 8)), dim3(256), 0, st, xa, xb, n, H, W, w1, bias, out);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// one 3x3 / s1 / p1 convolution on the mode-2 kernels; mask (with the optional addend): the ReLU mask of the result's layer in the
+// epilogue, where the dispatched kernel has one. `a` returns pool_applied / mask_applied.
+int conv3x3(hipStream_t st, const half_t* in, const half_t* w, half_t* out, int nimg, int H, int W, int cin, int cout, const float* bias, int act_out,
+            int pool2, const half_t* mask, const half_t* add, IgemmArgs& a) {
+  a = IgemmArgs{};
+  a.in = in; a.w = w; a.out = out;
+  a.bias = bias; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
+  a.n = nimg; a.Hs = H; a.Ws = W;
+  a.cin = cin; a.ldin = cin; a.coffin = 0;
+  a.cout = cout; a.ldout = cout; a.coffout = 0;
+  a.relu_in = 0; a.relu_cend = 0; a.act_out = act_out; a.force_splitk = 0;
+  a.pool2 = pool2;
+  if (mask) {
+    a.mask = mask; a.ldmask = cout; a.coffmask = 0; a.mask_slope = 0.f;
+    a.add = add; a.ldadd = cout; a.coffadd = 0;
+  }
+  return op_igemm(st, GI_F16, 2, a);
+}
+int maxpool2(hipStream_t st, const half_t* in, half_t* out, int nimg, int Ho, int Wo, int C) {
+  hipLaunchKernelGGL(maxpool2_kernel, dim3(nblk((int64_t)nimg * Ho * Wo * (C / 8), 256, 8192)), dim3(256), 0, st, in, out, nimg, Ho, Wo, C);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// Both terms of one tap (+ its dense Gram difference when dgram is given) from F [2n][HW][C]: gram2_kernel over `split` pixel ranges,
+// then the fixed-order reductions. The partial counts and the 1 / element counts of the two terms go to fin (terms tap and 5 + tap),
+// the partial sums to partial[tap * 1024 ..] and partial[(5 + tap) * 1024 ..]. force_split > 0 replaces the heuristic's first guess
+// (test seam); the workspace limits and the even division of the steps apply to it as to the heuristic's.
+int tap_terms(hipStream_t st, const half_t* F, int n, int64_t HW, int C, int tap, float* gram, int64_t gram_bytes, double* partial, VggFinP& fin,
+              float* dgram, unsigned* amax, int force_split, int* split_out) {
+  const int BLK = C >= 128 ? 128 : 64, nb_ = C / BLK, ntile = nb_ * (nb_ + 1) / 2;
+  const int steps = (int)((HW + 31) / 32);
+  int split = (512 + n * ntile - 1) / (n * ntile);
+  if (split > steps / 4) split = steps / 4;
+  if (force_split > 0) split = force_split < steps ? force_split : steps;
+  while (split > 1 && ((int64_t)2 * n * ntile * split * BLK * BLK * 4 > gram_bytes || n * nb_ * split > 1024)) --split;
+  if (split < 1) split = 1;
+  GI_REQUIRE((int64_t)2 * n * ntile * split * BLK * BLK * 4 <= gram_bytes && n * nb_ * split <= 1024, "vgg19: %d pairs exceed the Gram workspace", n);
+  Gram2P gp;
+  gp.F = (const char*)F; gp.P = gram; gp.sq = partial + tap * 1024;
+  gp.C = C; gp.HW = (int)HW; gp.n = n; gp.nblk = nb_; gp.ntile = ntile;
+  gp.steps_per_split = (steps + split - 1) / split;
+  split = (steps + gp.steps_per_split - 1) / gp.steps_per_split;
+  gp.split = split;
+  if (BLK == 128) {
+    static GiDevOnce attr;
+    if (attr.first()) { GI_HIP(hipFuncSetAttribute((const void*)gram2_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 32 * 288)); }
+    hipLaunchKernelGGL(gram2_kernel<64>, dim3(ntile, split, n), dim3(256), 2 * 4 * 32 * 288, st, gp);
+  } else {
+    hipLaunchKernelGGL(gram2_kernel<32>, dim3(ntile, split, n), dim3(256), 2 * 4 * 32 * 160, st, gp);
+  }
+  GI_LAUNCH_CHECK();
+  fin.nb[tap] = n * nb_ * split;
+  fin.inv[tap] = 1.0 / (double)((int64_t)n * HW * C);
+  const int nb2 = nblk((int64_t)n * ntile * BLK * BLK / 64, 1, 1024);
+  hipLaunchKernelGGL(gram2_diff_kernel, dim3(nb2), dim3(256), 0, st, (const float*)gram, n, nb_, ntile, split, BLK * BLK,
+                     (float)(1.0 / ((double)HW * C)), partial + (5 + tap) * 1024);
+  GI_LAUNCH_CHECK();
+  fin.nb[5 + tap] = nb2;
+  fin.inv[5 + tap] = 1.0 / (double)((int64_t)n * C * C);
+  if (dgram) {
+    hipLaunchKernelGGL(gram_delta_kernel, dim3(BLK * BLK / 256, ntile, n), dim3(256), 0, st, (const float*)gram, nb_, ntile, split, BLK, C,
+                       (float)(1.0 / ((double)HW * C)), dgram, amax);
+    GI_LAUNCH_CHECK();
+  }
+  if (split_out) *split_out = split;
+  return GI_OK;
+}
+int finish_terms(hipStream_t st, const double* partial, const VggFinP& fin, float* per_tap, float weight_p, float weight_s, float* out2) {
+  hipLaunchKernelGGL(vgg_finish_kernel, dim3(1), dim3(256), 0, st, partial, fin, per_tap, weight_p, weight_s, out2);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// one pass of a tap's seed over n pairs: store = false: max |seed| into smax (maps of more than kSeedSampleAll blocks are sampled),
+// store = true: s * seed over Ft
+int seed_pass(hipStream_t st, bool store, const half_t* Fo, half_t* Ft, const float* dg, const unsigned* dmax, unsigned* smax, const float* sc, int n,
+              int64_t HW, int C, float weight_p, float weight_s) {
+  SeedP p;
+  p.Fo = Fo; p.Ft = Ft; p.dg = dg; p.dmax = dmax; p.smax = smax; p.sc = sc;
+  p.C = C; p.HW = (int)HW; p.nb = (int)((HW + 255) / 256);
+  p.cp = (float)((double)weight_p * 2.0 / ((double)n * C * HW));
+  p.cs = (float)((double)weight_s * 4.0 / ((double)n * C * C * (double)HW * C));
+  const int nbx = !store && p.nb > kSeedSampleAll ? (p.nb + 7) / 8 : p.nb;      // the maximum pass samples large maps (vgg_seed_kernel)
+  const dim3 grid(nbx, C / 64, n);
+  if (!store) hipLaunchKernelGGL(vgg_seed_kernel<false>, grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(vgg_seed_kernel<true>, grid, dim3(256), 0, st, p);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int seed_scale(hipStream_t st, const unsigned* smax, float* sc) {
+  hipLaunchKernelGGL(vgg_scale_kernel, dim3(1), dim3(1), 0, st, smax, sc);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
+  if (pool) {
+    hipLaunchKernelGGL(vgg_act_bwd_kernel<true>, dim3(nblk((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H,
+                       W, C, relu);
+  } else {
+    hipLaunchKernelGGL(vgg_act_bwd_kernel<false>, dim3(nblk((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C, relu);
+  }
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int conv1_adjoint(hipStream_t st, const half_t* D, const float* w1, const float* sc, float gscale, float* dimg, int n, int H, int W) {
+  hipLaunchKernelGGL(vgg_conv1_adjoint_kernel, dim3((W + 31) / 32, (H + 15) / 16, n), dim3(256), 0, st, D, w1, sc, gscale, dimg, H, W);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+
 }  // namespace
 
 struct gi_vgg {
@@ -748,24 +878,16 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
   int H = v->H, W = v->W, cur = 0;
   half_t* curp = grad ? v->ga[0] : v->act[0];
   // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of gi_vgg19_create)
-  hipLaunchKernelGGL(vgg_conv1_mfma_kernel, dim3(nblk((int64_t)nimg * H * (W / 16), 4, 256 * 8)), dim3(256), 0, st, xa, xb, n, H, W, v->w1,
-                     v->params + v->boff[0], curp);
-  GI_LAUNCH_CHECK();
+  GI_TRY(conv1(st, xa, xb, n, H, W, v->w1, v->params + v->boff[0], curp));
   for (int i = 0; i < NCONV; ++i) {
     bool pooled = false;
     if (i > 0) {
-      IgemmArgs a = {};
+      IgemmArgs a;
       half_t* outp = grad ? v->ga[i] : v->act[cur ^ 1];
-      a.in = curp; a.w = v->wpk[i]; a.out = outp;
-      a.bias = v->params + v->boff[i]; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
-      a.n = nimg; a.Hs = H; a.Ws = W;
-      a.cin = kCin[i]; a.ldin = kCin[i]; a.coffin = 0;
-      a.cout = kCout[i]; a.ldout = kCout[i]; a.coffout = 0;
-      a.relu_in = 0; a.relu_cend = 0; a.act_out = GI_ACT_RELU; a.force_splitk = 0;
       // the pooled layers (conv1_2, conv2_2, conv3_4, conv4_4) are never taps: where the kernel can, it stores the 2x2 max pool of
       // its tile and the full-resolution map is never written
-      a.pool2 = (!grad && kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
-      GI_TRY(op_igemm(st, GI_F16, 2, a));
+      const int pool2 = (!grad && kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
+      GI_TRY(conv3x3(st, curp, v->wpk[i], outp, nimg, H, W, kCin[i], kCout[i], v->params + v->boff[i], GI_ACT_RELU, pool2, nullptr, nullptr, a));
       cur ^= 1;
       curp = outp;
       pooled = a.pool_applied != 0;
@@ -783,66 +905,21 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
       if (!feat_out) {
         // perceptual term mean over (n, C, H, W) of (F_o - F_t)^2 and style term mean over (n, C, C) of (G_o - G_t)^2, G = F^T F / (HW C):
         // one pass over the tap's feature maps (gram2_kernel) + the fixed-order reduction of its partial tiles
-        const int BLK = C >= 128 ? 128 : 64, nb_ = C / BLK, ntile = nb_ * (nb_ + 1) / 2;
-        const int steps = (int)((HW + 31) / 32);
-        int split = (512 + n * ntile - 1) / (n * ntile);
-        if (split > steps / 4) split = steps / 4;
-        while (split > 1 && ((int64_t)2 * n * ntile * split * BLK * BLK * 4 > v->gram_bytes || n * nb_ * split > 1024)) --split;
-        if (split < 1) split = 1;
-        GI_REQUIRE((int64_t)2 * n * ntile * split * BLK * BLK * 4 <= v->gram_bytes && n * nb_ * split <= 1024, "vgg19: %d pairs exceed the Gram workspace", n);
-        Gram2P gp;
-        gp.F = (const char*)F; gp.P = v->gram; gp.sq = v->partial + tap * 1024;
-        gp.C = C; gp.HW = (int)HW; gp.n = n; gp.nblk = nb_; gp.ntile = ntile;
-        gp.steps_per_split = (steps + split - 1) / split;
-        split = (steps + gp.steps_per_split - 1) / gp.steps_per_split;
-        gp.split = split;
-        if (BLK == 128) {
-          static GiDevOnce attr;
-          if (attr.first()) { GI_HIP(hipFuncSetAttribute((const void*)gram2_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 32 * 288)); }
-          hipLaunchKernelGGL(gram2_kernel<64>, dim3(ntile, split, n), dim3(256), 2 * 4 * 32 * 288, st, gp);
-        } else {
-          hipLaunchKernelGGL(gram2_kernel<32>, dim3(ntile, split, n), dim3(256), 2 * 4 * 32 * 160, st, gp);
-        }
-        GI_LAUNCH_CHECK();
-        v->fin.nb[tap] = n * nb_ * split;
-        v->fin.inv[tap] = 1.0 / (double)((int64_t)n * HW * C);
-        const int nb2 = nblk((int64_t)n * ntile * BLK * BLK / 64, 1, 1024);
-        hipLaunchKernelGGL(gram2_diff_kernel, dim3(nb2), dim3(256), 0, st, (const float*)v->gram, n, nb_, ntile, split, BLK * BLK,
-                           (float)(1.0 / ((double)HW * C)), v->partial + (5 + tap) * 1024);
-        GI_LAUNCH_CHECK();
-        v->fin.nb[5 + tap] = nb2;
-        v->fin.inv[5 + tap] = 1.0 / (double)((int64_t)n * C * C);
-        if (grad) {
-          hipLaunchKernelGGL(gram_delta_kernel, dim3(BLK * BLK / 256, ntile, n), dim3(256), 0, st, (const float*)v->gram, nb_, ntile, split, BLK, C,
-                             (float)(1.0 / ((double)HW * C)), v->dgram[tap], v->amax + tap);
-          GI_LAUNCH_CHECK();
-        }
+        GI_TRY(tap_terms(st, F, n, HW, C, tap, v->gram, v->gram_bytes, v->partial, v->fin, grad ? v->dgram[tap] : nullptr, grad ? v->amax + tap : nullptr,
+                         0, nullptr));
       }
     }
     if (kPoolAfter[i] && pooled) {
       H /= 2;
       W /= 2;
     } else if (kPoolAfter[i]) {
-      hipLaunchKernelGGL(maxpool2_kernel, dim3(nblk((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, curp,
-                         grad ? v->gpool[i] : v->act[cur ^ 1], nimg, H / 2, W / 2, C);
-      GI_LAUNCH_CHECK();
+      GI_TRY(maxpool2(st, curp, grad ? v->gpool[i] : v->act[cur ^ 1], nimg, H / 2, W / 2, C));
       curp = grad ? v->gpool[i] : v->act[cur ^ 1];
       cur ^= 1;
       H /= 2;
       W /= 2;
     }
   }
-  return GI_OK;
-}
-
-int act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
-  if (pool) {
-    hipLaunchKernelGGL(vgg_act_bwd_kernel<true>, dim3(nblk((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H,
-                       W, C, relu);
-  } else {
-    hipLaunchKernelGGL(vgg_act_bwd_kernel<false>, dim3(nblk((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C, relu);
-  }
-  GI_LAUNCH_CHECK();
   return GI_OK;
 }
 
@@ -855,23 +932,12 @@ int vgg_seeds(gi_vgg* v, int n, float weight_p, float weight_s) {
       const int tap = kTapAfter[i], C = kCout[i];
       if (tap >= 0) {
         const int64_t HW = (int64_t)H * W;
-        SeedP p;
-        p.Fo = v->ga[i]; p.Ft = v->ga[i] + (int64_t)n * HW * C; p.dg = v->dgram[tap]; p.dmax = v->amax + tap; p.smax = v->amax + 5; p.sc = v->sc;
-        p.C = C; p.HW = (int)HW; p.nb = (int)((HW + 255) / 256);
-        p.cp = (float)((double)weight_p * 2.0 / ((double)n * C * HW));
-        p.cs = (float)((double)weight_s * 4.0 / ((double)n * C * C * (double)HW * C));
-        const int nbx = pass == 0 && p.nb > kSeedSampleAll ? (p.nb + 7) / 8 : p.nb;      // pass 0: large maps are sampled (vgg_seed_kernel)
-        const dim3 grid(nbx, C / 64, n);
-        if (pass == 0) hipLaunchKernelGGL(vgg_seed_kernel<false>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(vgg_seed_kernel<true>, grid, dim3(256), 0, st, p);
-        GI_LAUNCH_CHECK();
+        GI_TRY(seed_pass(st, pass == 1, v->ga[i], v->ga[i] + (int64_t)n * HW * C, v->dgram[tap], v->amax + tap, v->amax + 5, v->sc, n, HW, C, weight_p,
+                         weight_s));
       }
       if (kPoolAfter[i]) { H /= 2; W /= 2; }
     }
-    if (pass == 0) {
-      hipLaunchKernelGGL(vgg_scale_kernel, dim3(1), dim3(1), 0, st, (const unsigned*)(v->amax + 5), v->sc);
-      GI_LAUNCH_CHECK();
-    }
+    if (pass == 0) GI_TRY(seed_scale(st, v->amax + 5, v->sc));
   }
   return GI_OK;
 }
@@ -896,16 +962,10 @@ int vgg_backward(gi_vgg* v, int n, int stop, float* layer_out, float* grad_out, 
   for (int l = NCONV - 1; l >= 1; --l) {
     const int below = l - 1;
     const bool pool = kPoolAfter[below] != 0, last = stop == below;
-    IgemmArgs a = {};
-    a.in = v->gbuf[cur]; a.w = v->wT[l]; a.out = v->gbuf[cur ^ 1];
-    a.n = n; a.Hs = Hl[l]; a.Ws = Wl[l];
-    a.cin = kCout[l]; a.ldin = kCout[l]; a.cout = kCin[l]; a.ldout = kCin[l];
-    a.act_out = GI_ACT_NONE;
-    if (!pool && !last) {     // the ReLU mask of the layer below (+ its seed) in the GEMM epilogue, where the dispatched kernel has one
-      a.mask = v->ga[below]; a.ldmask = kCin[l]; a.coffmask = 0; a.mask_slope = 0.f;
-      a.add = seed_of(below); a.ldadd = kCin[l]; a.coffadd = 0;
-    }
-    GI_TRY(op_igemm(st, GI_F16, 2, a));
+    IgemmArgs a;
+    const bool fuse = !pool && !last;     // the ReLU mask of the layer below (+ its seed) in the GEMM epilogue, where the dispatched kernel has one
+    GI_TRY(conv3x3(st, v->gbuf[cur], v->wT[l], v->gbuf[cur ^ 1], n, Hl[l], Wl[l], kCout[l], kCin[l], nullptr, GI_ACT_NONE, 0, fuse ? v->ga[below] : nullptr,
+                   fuse ? seed_of(below) : nullptr, a));
     if (pool) {
       GI_TRY(act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
     } else {
@@ -914,10 +974,7 @@ int vgg_backward(gi_vgg* v, int n, int stop, float* layer_out, float* grad_out, 
     }
     if (last) return readback(v->gbuf[cur], below);
   }
-  hipLaunchKernelGGL(vgg_conv1_adjoint_kernel, dim3((v->W + 31) / 32, (v->H + 15) / 16, n), dim3(256), 0, st, (const half_t*)v->gbuf[cur], (const float*)v->w1,
-                     (const float*)v->sc, gscale, grad_out, v->H, v->W);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
+  return conv1_adjoint(st, v->gbuf[cur], v->w1, v->sc, gscale, grad_out, n, v->H, v->W);
 }
 
 }  // namespace
@@ -973,19 +1030,10 @@ int gi_vgg19_bind(gi_vgg* v, const float* params, void* ws, int64_t ws_bytes) {
 int gi_vgg19_sync_weights(gi_vgg* v) {
   GI_REQUIRE(v && v->bound, "vgg19_sync_weights: not bound");
   hipStream_t st = v->ctx->stream;
-  hipLaunchKernelGGL(sum_cin_kernel, dim3(3), dim3(256), 0, st, v->params + v->woff[0], v->w1, 64, 3);
-  GI_LAUNCH_CHECK();
-  for (int i = 1; i < NCONV; ++i) {
-    hipLaunchKernelGGL(pack3x3_kernel, dim3(nblk((int64_t)kCout[i] * 9 * kCin[i], 256, 2048)), dim3(256), 0, st, v->params + v->woff[i],
-                       v->wpk[i], kCout[i], kCin[i]);
-    GI_LAUNCH_CHECK();
-  }
+  GI_TRY(sum_cin(st, v->params + v->woff[0], v->w1));
+  for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, false, v->params + v->woff[i], v->wpk[i], kCout[i], kCin[i]));
   if (v->gbound) {     // the transposed convolutions' weights, only for a handle that can run the backward
-    for (int i = 1; i < NCONV; ++i) {
-      hipLaunchKernelGGL(pack3x3_t_kernel, dim3(nblk((int64_t)kCout[i] * 9 * kCin[i], 256, 2048)), dim3(256), 0, st, v->params + v->woff[i],
-                         v->wT[i], kCout[i], kCin[i]);
-      GI_LAUNCH_CHECK();
-    }
+    for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, true, v->params + v->woff[i], v->wT[i], kCout[i], kCin[i]));
   }
   v->synced = true;
   return GI_OK;
@@ -996,8 +1044,7 @@ int gi_vgg19_perceptual_style(gi_vgg* v, const float* output, const float* targe
   GI_REQUIRE(v && v->bound && v->synced, "vgg19_perceptual_style: bind + sync_weights first");
   GI_REQUIRE(output && target && out2 && n > 0 && n <= v->max_pairs, "vgg19_perceptual_style: n=%d (max %d)", n, v->max_pairs);
   GI_TRY(vgg_run(v, output, target, n, -1, nullptr));
-  hipLaunchKernelGGL(vgg_finish_kernel, dim3(1), dim3(256), 0, v->ctx->stream, (const double*)v->partial, v->fin, v->per_tap, weight_p, weight_s, out2);
-  GI_LAUNCH_CHECK();
+  GI_TRY(finish_terms(v->ctx->stream, v->partial, v->fin, v->per_tap, weight_p, weight_s, out2));
   if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, v->ctx->stream));
   return GI_OK;
 }
@@ -1024,8 +1071,7 @@ int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* 
   v->grad_n = 0;
   GI_HIP(hipMemsetAsync(v->amax, 0, 256, st));
   GI_TRY(vgg_run(v, output, target, n, -1, nullptr, true));
-  hipLaunchKernelGGL(vgg_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)v->partial, v->fin, v->per_tap, weight_p, weight_s, out2);
-  GI_LAUNCH_CHECK();
+  GI_TRY(finish_terms(st, v->partial, v->fin, v->per_tap, weight_p, weight_s, out2));
   if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, st));
   GI_TRY(vgg_seeds(v, n, weight_p, weight_s));
   v->grad_n = n;
@@ -1048,6 +1094,95 @@ int gi_vgg19_features(gi_vgg* v, const float* x, int n, int tap, float* out_nchw
   // the runner works on 2n stacked images: feed x twice, return the first n
   GI_TRY(vgg_run(v, x, x, n, tap, out_nchw));
   return GI_OK;
+}
+
+// ---- the loss path's kernels one at a time (test seam; include/ganinpaint.h). Every entry checks what its kernel assumes and goes
+// through the host launch code above; nothing here is on a training path ----------------------------------------------------------
+#define GI_VGG_FITS31(count) ((int64_t)(count) > 0 && (int64_t)(count) < (1ll << 31))
+
+int gi_debug_vgg_conv3x3(gi_ctx* ctx, const void* in, const float* w, void* w_packed, void* out, int n, int H, int W, int cin, int cout, int transposed,
+                         const float* bias, int act_out, int pool2, const void* mask, const void* add, int* pool_applied, int* mask_applied) {
+  GI_REQUIRE(ctx && in && w && w_packed && out && pool_applied && mask_applied, "debug_vgg_conv3x3: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && cin > 0 && cout > 0 && cin % 64 == 0 && cout % 64 == 0, "debug_vgg_conv3x3: n=%d H=%d W=%d cin=%d cout=%d (channels: multiples of 64)",
+             n, H, W, cin, cout);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)n * H * W * (cin > cout ? cin : cout)) && GI_VGG_FITS31((int64_t)cin * 9 * cout), "debug_vgg_conv3x3: tensor beyond 32-bit offsets");
+  GI_REQUIRE(act_out == GI_ACT_NONE || act_out == GI_ACT_RELU, "debug_vgg_conv3x3: act_out=%d", act_out);
+  GI_REQUIRE(!pool2 || (H % 2 == 0 && W % 2 == 0), "debug_vgg_conv3x3: pool2 needs even H=%d W=%d", H, W);
+  GI_REQUIRE(mask || !add, "debug_vgg_conv3x3: add without mask");
+  hipStream_t st = ctx->stream;
+  GI_TRY(pack3x3(st, transposed != 0, w, (half_t*)w_packed, cout, cin));
+  IgemmArgs a;
+  const int ci = transposed ? cout : cin, co = transposed ? cin : cout;     // the input gradient: the channel roles swap
+  const int rc = conv3x3(st, (const half_t*)in, (const half_t*)w_packed, (half_t*)out, n, H, W, ci, co, bias, act_out, pool2 ? 1 : 0, (const half_t*)mask,
+                         (const half_t*)add, a);
+  if (rc == GI_ERR_UNSUPPORTED) gi_set_error("debug_vgg_conv3x3: no mode-2 kernel serves n=%d %dx%d %d->%d", n, H, W, ci, co);
+  GI_TRY(rc);
+  *pool_applied = a.pool_applied; *mask_applied = a.mask_applied;
+  return GI_OK;
+}
+
+int gi_debug_vgg_conv1(gi_ctx* ctx, const float* xa, const float* xb, int n, int H, int W, const float* w, const float* bias, float* w1, void* out) {
+  GI_REQUIRE(ctx && xa && xb && w && bias && w1 && out, "debug_vgg_conv1: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && W % 16 == 0, "debug_vgg_conv1: n=%d H=%d W=%d (W: a multiple of 16)", n, H, W);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)2 * n * H * W * 64), "debug_vgg_conv1: tensor beyond 32-bit offsets");
+  GI_TRY(sum_cin(ctx->stream, w, w1));
+  return conv1(ctx->stream, xa, xb, n, H, W, w1, bias, (half_t*)out);
+}
+
+int gi_debug_vgg_maxpool2(gi_ctx* ctx, const void* in, void* out, int nimg, int Ho, int Wo, int C) {
+  GI_REQUIRE(ctx && in && out, "debug_vgg_maxpool2: null pointer");
+  GI_REQUIRE(nimg > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, "debug_vgg_maxpool2: nimg=%d Ho=%d Wo=%d C=%d (C: a multiple of 8)", nimg, Ho, Wo, C);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)nimg * Ho * Wo * 4 * C), "debug_vgg_maxpool2: tensor beyond 32-bit offsets");
+  return maxpool2(ctx->stream, (const half_t*)in, (half_t*)out, nimg, Ho, Wo, C);
+}
+
+int64_t gi_debug_vgg_tap_ws_bytes(void) { return 10 * 1024 * 8 + 256 + (32ll << 20); }
+
+int gi_debug_vgg_tap_terms(gi_ctx* ctx, const void* F, int n, int HW, int C, int force_split, void* ws, int64_t ws_bytes, float* terms2, float* dg,
+                           unsigned* amax, int* split_out) {
+  GI_REQUIRE(ctx && F && ws && terms2 && split_out, "debug_vgg_tap_terms: null pointer");
+  GI_REQUIRE((dg != nullptr) == (amax != nullptr), "debug_vgg_tap_terms: dg and amax go together");
+  GI_REQUIRE(n > 0 && HW > 0 && (C == 64 || (C > 0 && C % 128 == 0)) && force_split >= 0, "debug_vgg_tap_terms: n=%d HW=%d C=%d (64 or a multiple of 128) split=%d", n, HW,
+             C, force_split);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)2 * n * HW * C) && GI_VGG_FITS31((int64_t)n * C * C), "debug_vgg_tap_terms: tensor beyond 32-bit offsets");
+  GI_REQUIRE(ws_bytes >= gi_debug_vgg_tap_ws_bytes() && ((uintptr_t)ws & 255) == 0, "debug_vgg_tap_terms: workspace %lld bytes (need %lld, 256-byte aligned)",
+             (long long)ws_bytes, (long long)gi_debug_vgg_tap_ws_bytes());
+  hipStream_t st = ctx->stream;
+  double* partial = (double*)ws;                                  // [10 terms][1024], as gi_vgg's
+  float* per_tap = (float*)((char*)ws + 10 * 1024 * 8);
+  float* gram = (float*)((char*)ws + 10 * 1024 * 8 + 256);
+  VggFinP fin = {};                                               // the other four taps: no partials, terms of zero
+  if (amax) GI_HIP(hipMemsetAsync(amax, 0, 4, st));
+  GI_TRY(tap_terms(st, (const half_t*)F, n, HW, C, 0, gram, ws_bytes - (10 * 1024 * 8 + 256), partial, fin, dg, amax, force_split, split_out));
+  return finish_terms(st, partial, fin, per_tap, 1.f, 1.f, terms2);
+}
+
+int gi_debug_vgg_seed(gi_ctx* ctx, int store, const void* Fo, void* Ft, const float* dg, const unsigned* dmax, unsigned* smax, const float* sc, int n, int HW,
+                      int C, float weight_p, float weight_s) {
+  GI_REQUIRE(ctx && Fo && Ft && dg && dmax && (store ? sc != nullptr : smax != nullptr), "debug_vgg_seed: null pointer");
+  GI_REQUIRE(n > 0 && HW > 0 && C > 0 && C % 64 == 0, "debug_vgg_seed: n=%d HW=%d C=%d (a multiple of 64)", n, HW, C);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)n * HW * C) && GI_VGG_FITS31((int64_t)n * C * C), "debug_vgg_seed: tensor beyond 32-bit offsets");
+  return seed_pass(ctx->stream, store != 0, (const half_t*)Fo, (half_t*)Ft, dg, dmax, smax, sc, n, HW, C, weight_p, weight_s);
+}
+
+int gi_debug_vgg_scale(gi_ctx* ctx, const unsigned* smax, float* sc) {
+  GI_REQUIRE(ctx && smax && sc, "debug_vgg_scale: null pointer");
+  return seed_scale(ctx->stream, smax, sc);
+}
+
+int gi_debug_vgg_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W, int C, int relu) {
+  GI_REQUIRE(ctx && act && out, "debug_vgg_act_bwd: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "debug_vgg_act_bwd: n=%d H=%d W=%d C=%d (C: a multiple of 8)", n, H, W, C);
+  GI_REQUIRE(GI_VGG_FITS31((int64_t)n * H * W * C), "debug_vgg_act_bwd: tensor beyond 32-bit offsets");
+  GI_REQUIRE(!pool || (g && !seed && out != g && H % 2 == 0 && W % 2 == 0), "debug_vgg_act_bwd: the pool form needs g, no seed, out apart from g and even H=%d W=%d",
+             H, W);
+  return act_bwd(ctx->stream, pool != 0, (const half_t*)g, (const half_t*)act, (const half_t*)seed, (half_t*)out, n, H, W, C, relu);
+}
+
+int gi_debug_vgg_conv1_adjoint(gi_ctx* ctx, const void* D, const float* w1, const float* sc, float gscale, float* dimg, int n, int H, int W) {
+  GI_REQUIRE(ctx && D && w1 && sc && dimg, "debug_vgg_conv1_adjoint: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && GI_VGG_FITS31((int64_t)n * H * W * 64), "debug_vgg_conv1_adjoint: n=%d H=%d W=%d", n, H, W);
+  return conv1_adjoint(ctx->stream, (const half_t*)D, w1, sc, gscale, dimg, n, H, W);
 }
 
 }  // extern "C"

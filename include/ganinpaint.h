@@ -685,6 +685,42 @@ int gi_debug_gp_unscale_add(gi_ctx* ctx, const float* src, const float* sc, floa
  * one workgroup per row and one lane per channel as the producing kernels do */
 int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends,
                           int rows);
+/* ---- the VGG-19 loss path's kernels on their own (test seam) ------------------------------------------------------------------
+ * Each entry checks what its kernel assumes (GI_ERR_INVALID before any launch) and runs the host launch code of csrc/vgg.hip that the
+ * network runners use; nothing here is on a training path. Feature maps are dense NHWC fp16; tests/vgg_ops_ref.py restates every op.
+ * conv3x3: one 3x3 / s1 / p1 convolution on the mode-2 implicit GEMMs. w: fp32 master [cout][cin][3][3], packed into w_packed
+ * (cout * 9 * cin halves) first. transposed = 0: in (n,H,W,cin) -> out (n,H,W,cout) = act_out(bias + conv). transposed = 1: the input
+ * gradient, in (n,H,W,cout) -> out (n,H,W,cin). bias, mask, add (each may be NULL) have the OUTPUT's channels: with mask the result is
+ * [mask > 0] * (conv + add) where the serving kernel has that epilogue (*mask_applied = 1), the plain convolution otherwise. pool2:
+ * where the kernel can (*pool_applied = 1), `out` receives the (n,H/2,W/2,.) max pool instead. gi_debug_last_kernel() names the kernel. */
+int gi_debug_vgg_conv3x3(gi_ctx* ctx, const void* in, const float* w, void* w_packed, void* out, int n, int H, int W, int cin,
+                         int cout, int transposed, const float* bias, int act_out, int pool2, const void* mask, const void* add,
+                         int* pool_applied, int* mask_applied);
+/* conv1_1 on the replicated grey images xa, xb (n,H,W fp32 each): w [64][3][3][3], w1 [64][9] receives the weights summed over the
+ * input channel, out [2n][H][W][64] fp16 = relu(bias + conv) */
+int gi_debug_vgg_conv1(gi_ctx* ctx, const float* xa, const float* xb, int n, int H, int W, const float* w, const float* bias,
+                       float* w1, void* out);
+int gi_debug_vgg_maxpool2(gi_ctx* ctx, const void* in, void* out, int nimg, int Ho, int Wo, int C);   /* in (nimg,2Ho,2Wo,C) */
+/* both terms of one tap from F [2n][HW][C] (output images, then target images): terms2 = {mean (F_o - F_t)^2, mean (G_o - G_t)^2},
+ * G = F^T F / (HW C); with dg / amax (both or neither): the dense dg [n][C][C] = G_o - G_t and the bit pattern of max |dg|.
+ * force_split > 0 replaces the first guess of the pixel-range split; *split_out: the split that ran. ws: gi_debug_vgg_tap_ws_bytes()
+ * bytes, 256-byte aligned. */
+int64_t gi_debug_vgg_tap_ws_bytes(void);
+int gi_debug_vgg_tap_terms(gi_ctx* ctx, const void* F, int n, int HW, int C, int force_split, void* ws, int64_t ws_bytes,
+                           float* terms2, float* dg, unsigned* amax, int* split_out);
+/* seed of a tap, d(weight_p P + weight_s S) / dF_o, from Fo, Ft [n][HW][C], dg [n][C][C] and dmax (bit pattern of max |dg|).
+ * store = 0: *smax = max(*smax, max |seed|) as a bit pattern (maps of more than 2048 pixels: over one 256-pixel block of eight);
+ * store = 1: sc[0] * seed in fp16 over Ft. scale: sc = {s, 1 / s}, s the power of two that puts *smax into [2^-3, 2^-2). */
+int gi_debug_vgg_seed(gi_ctx* ctx, int store, const void* Fo, void* Ft, const float* dg, const unsigned* dmax, unsigned* smax,
+                      const float* sc, int n, int HW, int C, float weight_p, float weight_s);
+int gi_debug_vgg_scale(gi_ctx* ctx, const unsigned* smax, float* sc);
+/* pool = 0: out = [act > 0 or !relu] * (g + seed), g / seed may be NULL, out may be g. pool = 1: g (n,H/2,W/2,C) routed to the first
+ * maximum of every 2x2 window of act (n,H,W,C), times [max > 0 or !relu]; zeros elsewhere */
+int gi_debug_vgg_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W,
+                         int C, int relu);
+/* dimg (n,H,W fp32) = gscale * sc[1] * adjoint of the 1 -> 64 convolution w1 [64][9] applied to D (n,H,W,64) fp16 */
+int gi_debug_vgg_conv1_adjoint(gi_ctx* ctx, const void* D, const float* w1, const float* sc, float gscale, float* dimg, int n,
+                               int H, int W);
 /* fp32 master [a][16][b] -> T [a][16*b] (w_packed) and T [4][b][4*a] (w_phase); either may be NULL */
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase);
 int gi_convert(gi_ctx* ctx, int dtype, const float* src, void* dst, int64_t count);      /* fp32 -> T */
