@@ -31,6 +31,8 @@ PROTOTYPES = {
     "gi_unet_create_norm": (_i, [_vp, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "gi_unet_create_padded": (_i, [_vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "gi_patchgan_create": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "gi_patchgan_create_sn": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "gi_net_sn_read": (_i, [_vp, _i, _vp, _vp, _i64]),
     "gi_dcgan_create": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "gi_dcgan_debug_forward_convs": (_i, [_vp, _i, _vp, _i]),
     "gi_net_destroy": (_i, [_vp]),
@@ -168,6 +170,8 @@ PROTOTYPES = {
     "gi_debug_bn_tangent_inject": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "gi_debug_gp_direction": (_i, [_vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp, _vp]),
     "gi_debug_gp_unscale_add": (_i, [_vp, _vp, _vp, _vp, _i64]),
+    "gi_debug_sn_power_iteration": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "gi_debug_sn_project_add": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "gi_debug_stat_acc_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
     "gi_debug_vgg_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "gi_debug_vgg_conv1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -496,3 +496,43 @@ int op_gp_direction(hipStream_t st, const float* g, int n, int64_t hw, float lam
                     float* sc);
 // dst += src * sc[1] (count floats)
 int op_gp_unscale_add(hipStream_t st, const float* src, const float* sc, float* dst, int64_t count);
+
+// spectral normalisation (specnorm.hip), fp32 throughout. One tensor = a ca x K row-major matrix W; cb > 0: a 4x4 convolution
+// weight in the master layout [a][ky][kx][b] (K = 16 cb), whose memory column kk * cb + b is column b * 16 + kk of v (torch's
+// weight.view(ca, -1) order); cb == 0: plain row-major. Every launch takes ONE table over all tensors.
+struct SnJob {
+  const float* w = nullptr;   // the matrix (power iteration: master weights; projection: the effective weights W / sigma)
+  float* u = nullptr;         // [ca] (power iteration: updated in place in train mode)
+  float* v = nullptr;         // [K], torch's column order
+  float* sigma = nullptr;     // one float (power iteration: written; projection: read)
+  int ca = 0, K = 0, cb = 0;
+  // power-iteration scratch (op_sn_scratch_floats, op_sn_carve): fixed-order partial sums
+  float* part_t = nullptr;    // [rchunks][K]  W^T u over 16-row chunks
+  float* t_raw = nullptr;     // [K]           W^T u, torch's column order, not yet normalised
+  float* nrm_part = nullptr;  // [ctiles]      sum of squares of t per 256-column tile
+  float* part_s = nullptr;    // [ca][cchunks] W v over 1024-column chunks
+  float* s_vec = nullptr;     // [ca]          W v
+  int rchunks = 0, ctiles = 0, cchunks = 0;
+  // projection (the accumulation itself runs over the flat buffers: SnSegs)
+  const float* g = nullptr;   // [ca][K] dL/dW_eff
+  float* dot_part = nullptr;  // [dchunks] partial sums of <G, W_eff> over 4096-element chunks
+  float* c = nullptr;         // one float: <G, W_eff>
+  int dchunks = 0;
+  // first workgroup of this tensor in the launches whose grid is split by tensor: [0..2] the power iteration's W^T u partial,
+  // W^T u finish and W v launches, [3] the projection's <G, W_eff> partial launch
+  int blk[4] = {0, 0, 0, 0};
+};
+struct SnJobs { SnJob j[6]; int n = 0; };
+int64_t op_sn_scratch_floats(int ca, int K);          // power iteration + projection scratch of one tensor
+void op_sn_carve(SnJob& J, float* scratch);           // points the scratch members of J (ca, K set) into `scratch`
+// train: `iters` times v = W^T u / max(|W^T u|, 1e-12), u = W v / max(|W v|, 1e-12); then sigma = u . (W v). eval: only sigma
+int op_sn_power_iteration(hipStream_t st, SnJobs& P, int iters, int train);
+// the same tensors as ranges [off, off + numel) of a flat parameter-shaped buffer (the elementwise passes; c: SnJob::c)
+struct SnSeg { int64_t off, numel; const float* sigma; int ca, K, cb; const float* u; const float* v; const float* c; };
+struct SnSegs { SnSeg s[6]; int n = 0; };
+// dst[0, count) = src with the elements of the table's tensors divided by *sigma (off, numel, sigma read)
+int op_sn_effective(hipStream_t st, const float* src, float* dst, int64_t count, const SnSegs& S);
+// c = <G, W_eff> per tensor (fixed order), then over the flat range [lo, hi): dst += scale * (G - c u v^T) / sigma inside the
+// table's tensors and dst += scale * G elsewhere; scale = scale_dev ? *scale_dev : 1. Jobs: g / w (effective) / dot_part / c set
+int op_sn_project_add(hipStream_t st, SnJobs& P, const SnSegs& S, const float* g_flat, float* dst_flat, int64_t lo, int64_t hi,
+                      const float* scale_dev);

@@ -16,7 +16,7 @@ namespace {
 
 struct TensorDesc {
   std::string name;
-  int kind;  // 0 conv weight, 1 contiguous param, 2 running_mean, 3 running_var
+  int kind;  // 0 conv weight, 1 contiguous param, 2 running_mean, 3 running_var, 4 plain buffer (spectral norm u / v)
   int64_t shape[4];
   int ndim;
   int64_t offset, numel;
@@ -159,6 +159,17 @@ struct gi_net {
   int64_t oD2 = -1, oTZ = -1, oGimg = -1, oVimg = -1, oGPs = -1, oGPpart = -1, oGPsums = -1, oTh = -1;
   int64_t oGPgrad = -1;              // n_params floats: the penalty's parameter gradients at tangent scale, before the 1/s add
   int gp_slot = -1;
+  // spectral normalisation (patchgan, gi_patchgan_create_sn; specnorm.hip). The kernels of a forward / backward read the EFFECTIVE
+  // parameters (oSnEff: the six weights divided by their sigma, everything else copied) because `params` points there for the
+  // duration (ParamsBack); `master` keeps the bound buffer. A backward writes gradients with respect to the effective weights into
+  // oSnGrad and sn_project folds them into the bound ones. Per slot (oSnSlot): the u | v the forward ended with, then its six sigma.
+  int sn = 0, sn_iters = 1;
+  struct SnTensor { int64_t off = 0, u_off = 0, v_off = 0, scratch = 0; int ca = 0, K = 0, cb = 0; } snt[6];
+  int64_t oSnEff = -1, oSnGrad = -1, oSnSlot = -1;
+  int64_t sn_uv_off = 0, sn_uv_floats = 0;   // the u / v buffers: one contiguous range of the flat buffer allocation
+  uint64_t sn_gen = 0, sn_eff_gen = 0;       // forwards so far; the forward whose sigma the effective (and packed) copies hold
+  std::vector<uint64_t> slot_sn_gen;
+  float* master = nullptr;
   std::vector<int> slot_n, slot_train, slot_groups;
   std::vector<std::vector<const uint8_t*>> ext_mask;  // [slot][level]
 
@@ -402,33 +413,51 @@ extern "C" int gi_unet_create(gi_ctx* ctx, int num_downs, int ngf, float dropout
   return gi_unet_create_ex(ctx, num_downs, ngf, 1, dropout_p, H, W, max_n, dtype, n_slots, out);
 }
 
-extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int max_n, int dtype, int n_slots, gi_net** out) {
+extern "C" int gi_patchgan_create_sn(gi_ctx* ctx, int H, int W, int sigmoid, int spectral_norm, int n_power_iterations, int max_n, int dtype,
+                                    int n_slots, gi_net** out) {
   GI_REQUIRE(out, "patchgan_create: null argument");  // ctx may be null: inventory-only handle
+  GI_REQUIRE(!spectral_norm || n_power_iterations >= 1, "patchgan_create: n_power_iterations=%d", n_power_iterations);
   GI_REQUIRE(dtype == GI_F16 || dtype == GI_F32, "patchgan_create: dtype=%d", dtype);
   GI_REQUIRE(H >= 64 && W >= 64 && H % 16 == 0 && W % 16 == 0, "patchgan_create: H=%d W=%d must be multiples of 16, >= 64", H, W);
   GI_REQUIRE(max_n >= 1 && n_slots >= 1 && n_slots <= 8, "patchgan_create: max_n=%d n_slots=%d", max_n, n_slots);
   gi_net* net = new gi_net();
   net->ctx = ctx; net->kind = 1; net->dtype = dtype; net->H = H; net->W = W; net->max_n = max_n; net->n_slots = n_slots;
   net->sigmoid = sigmoid;
+  net->sn = spectral_norm ? 1 : 0; net->sn_iters = n_power_iterations;
   net->loss_scale = dtype == GI_F16 ? 65536.f : 1.f;
   net->Hh = H / 16; net->Wh = W / 16;
   net->P = (net->Hh - 3) * (net->Wh - 3);
   const int chans[5] = {1, 64, 128, 256, 512};
   const int conv_idx[5] = {0, 0, 2, 5, 8};
   const int bn_idx[5] = {0, 0, 3, 6, 9};
+  const std::string wname = net->sn ? ".weight_orig" : ".weight";
   std::vector<std::pair<std::string, BN*>> bns;
   for (int i = 1; i <= 4; ++i) {
     Conv& c = net->dconv[i];
     c.ca = chans[i]; c.cb = chans[i - 1];
-    add_tensor(net, "model." + std::to_string(conv_idx[i]) + ".weight", 0, {c.ca, c.cb, 4, 4}, &c.w_off);
+    add_tensor(net, "model." + std::to_string(conv_idx[i]) + wname, 0, {c.ca, c.cb, 4, 4}, &c.w_off);
     if (i >= 2) add_bn(net, "model." + std::to_string(bn_idx[i]), net->dbn[i], chans[i], bns);
   }
-  add_tensor(net, "model.11.weight", 0, {1, 512, 4, 4}, &net->w5_off);
-  add_tensor(net, "model.13.weight", 1, {1, net->P}, &net->wl_off);
+  add_tensor(net, "model.11" + wname, 0, {1, 512, 4, 4}, &net->w5_off);
+  add_tensor(net, "model.13" + wname, 1, {1, net->P}, &net->wl_off);
   add_tensor(net, "model.13.bias", 1, {1}, &net->bl_off);
   for (auto& pb : bns) {
     add_tensor(net, pb.first + ".running_mean", 2, {pb.second->c}, &pb.second->rmean_off);
     add_tensor(net, pb.first + ".running_var", 3, {pb.second->c}, &pb.second->rvar_off);
+  }
+  if (net->sn) {   // the normalised tensors as ca x K matrices, and their u / v buffers (torch's names)
+    const int layer[6] = {0, 2, 5, 8, 11, 13};
+    for (int t = 0; t < 6; ++t) {
+      gi_net::SnTensor& T = net->snt[t];
+      if (t < 4) { T.off = net->dconv[t + 1].w_off; T.ca = chans[t + 1]; T.cb = chans[t]; T.K = 16 * T.cb; }
+      else if (t == 4) { T.off = net->w5_off; T.ca = 1; T.cb = 512; T.K = 8192; }
+      else { T.off = net->wl_off; T.ca = 1; T.cb = 0; T.K = net->P; }
+      const std::string base = "model." + std::to_string(layer[t]);
+      add_tensor(net, base + ".weight_u", 4, {T.ca}, &T.u_off);
+      add_tensor(net, base + ".weight_v", 4, {T.K}, &T.v_off);
+    }
+    net->sn_uv_off = net->snt[0].u_off;
+    net->sn_uv_floats = net->n_buffers - net->sn_uv_off;
   }
   const int64_t T = (int64_t)net->tsz();
   Arena& A = net->arena;
@@ -487,7 +516,13 @@ extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int ma
     net->oGPsums = A.take(5 * 512 * 4);
     net->oTh = A.take(N * net->P * 4 * 2);
   }
+  if (net->sn) {
+    net->oSnEff = A.take(net->n_params * 4);
+    net->oSnGrad = A.take(net->n_params * 4);
+    for (gi_net::SnTensor& t : net->snt) t.scratch = A.take(op_sn_scratch_floats(t.ca, t.K) * 4);
+  }
   Arena S;
+  if (net->sn) net->oSnSlot = S.take((net->sn_uv_floats + 64) * 4);
   for (int i = 1; i <= 4; ++i) net->oA[i] = S.take(N * (H >> i) * (W >> i) * chans[i] * T);
   for (int i = 2; i <= 4; ++i) net->oRd[i] = S.take(N * (H >> i) * (W >> i) * chans[i] * T);
   net->oHh = S.take(N * net->P * 4);
@@ -512,8 +547,13 @@ extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int ma
   net->slot_bits1.assign(n_slots + 1, 0);
   net->fuse_head = gi_opt(GI_OPT_FUSE_HEAD);
   net->slot_groups.assign(n_slots + 1, 1);
+  net->slot_sn_gen.assign(n_slots + 1, 0);
   *out = net;
   return GI_OK;
+}
+
+extern "C" int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int max_n, int dtype, int n_slots, gi_net** out) {
+  return gi_patchgan_create_sn(ctx, H, W, sigmoid, 0, 1, max_n, dtype, n_slots, out);
 }
 
 // a kind-2 handle for gi_dcgan_create (dcgan.hip): inventory entries through gi_net_add_param, workspace size from dcgan.hip
@@ -583,8 +623,9 @@ extern "C" int gi_net_bind(gi_net* net, float* params, float* grads, float* buff
   GI_REQUIRE(workspace_bytes >= net->arena.size, "net_bind: workspace %lld < required %lld", (long long)workspace_bytes,
              (long long)net->arena.size);
   GI_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)params & 15) == 0, "net_bind: workspace must be 256-byte aligned");
-  net->params = params; net->grads = grads; net->buffers = buffers; net->ws = (char*)workspace;
+  net->params = net->master = params; net->grads = grads; net->buffers = buffers; net->ws = (char*)workspace;
   net->bound = true;
+  net->sn_eff_gen = 0;
   if (net->acc_words > 0) GI_HIP(hipMemsetAsync(net->shared(net->oAcc), 0, (size_t)net->acc_words * 8, net->ctx->stream));
   if (net->oTickets >= 0) GI_HIP(hipMemsetAsync(net->shared(net->oTickets), 0, (size_t)GI_IGEMM_TICKETS * 4, net->ctx->stream));
   return GI_OK;
@@ -595,6 +636,81 @@ const void* packed_ptr(const gi_net* net, const Conv& c) {
   return c.packed_off == -2 ? (const void*)(net->params + c.w_off) : (const void*)net->shared(c.packed_off);
 }
 const void* phase_ptr(const gi_net* net, const Conv& c) { return net->shared(c.phase_off); }
+
+void pack_job(const gi_net* net, const Conv& c, PackJobs& P) {
+  PackJob& J = P.j[P.n++];
+  J.w = net->params + c.w_off; J.ca = c.ca; J.cb = c.cb; J.tile0 = 0; J.scale_on_b = 0; J.scale = nullptr;
+  J.packed = c.packed_off >= 0 ? (void*)net->shared(c.packed_off) : nullptr;
+  J.phase = net->shared(c.phase_off);
+}
+
+// ---- spectral normalisation (gi_net::sn) ----
+// net->params points at the effective parameters while a forward / backward / penalty of such a handle runs
+struct ParamsBack { gi_net* net; float* p; ~ParamsBack() { net->params = p; } };
+
+float* sn_slot_uv(const gi_net* net, int s) { return (float*)net->slot(s, net->oSnSlot); }
+float* sn_slot_sigma(const gi_net* net, int s) { return sn_slot_uv(net, s) + net->sn_uv_floats; }
+
+SnSegs sn_segs(const gi_net* net, int s, int64_t lo, int64_t hi) {
+  SnSegs S;
+  for (int t = 0; t < 6; ++t) {
+    const gi_net::SnTensor& T = net->snt[t];
+    if (T.off < lo || T.off >= hi) continue;
+    const float* uv = sn_slot_uv(net, s);
+    S.s[S.n++] = SnSeg{T.off, (int64_t)T.ca * T.K, sn_slot_sigma(net, s) + t, T.ca, T.K, T.cb, uv + (T.u_off - net->sn_uv_off),
+                       uv + (T.v_off - net->sn_uv_off), nullptr};
+  }
+  return S;
+}
+
+// Points net->params at the effective parameters of slot s's forward and re-derives them, and the packed copies, unless they
+// already hold that forward's. fresh: this IS the forward - power iteration on the master weights (train mode; eval mode: sigma of
+// the stored u, v), the slot keeps u | v | sigma. The caller holds a ParamsBack.
+int sn_enter(gi_net* net, int s, bool fresh) {
+  hipStream_t st = net->ctx->stream;
+  float* eff = (float*)net->shared(net->oSnEff);
+  if (fresh) {
+    SnJobs P;
+    P.n = 6;
+    for (int t = 0; t < 6; ++t) {
+      const gi_net::SnTensor& T = net->snt[t];
+      SnJob& J = P.j[t];
+      J.w = net->master + T.off; J.u = net->buffers + T.u_off; J.v = net->buffers + T.v_off; J.sigma = sn_slot_sigma(net, s) + t;
+      J.ca = T.ca; J.K = T.K; J.cb = T.cb;
+      op_sn_carve(J, (float*)net->shared(T.scratch));
+    }
+    GI_TRY(op_sn_power_iteration(st, P, net->sn_iters, net->train));
+    GI_HIP(hipMemcpyAsync(sn_slot_uv(net, s), net->buffers + net->sn_uv_off, (size_t)net->sn_uv_floats * 4, hipMemcpyDeviceToDevice, st));
+    net->slot_sn_gen[s] = ++net->sn_gen;
+  }
+  net->params = eff;
+  if (net->sn_eff_gen == net->slot_sn_gen[s]) return GI_OK;
+  GI_TRY(op_sn_effective(st, net->master, eff, net->n_params, sn_segs(net, s, 0, net->n_params)));
+  PackJobs P;
+  P.n = 0;
+  for (int i = 2; i <= 4; ++i) pack_job(net, net->dconv[i], P);
+  GI_TRY(op_pack_weights_batch(st, net->dtype, P));
+  net->sn_eff_gen = net->slot_sn_gen[s];
+  return GI_OK;
+}
+
+// dst[lo, hi) += scale * (projection of g through slot s's u, v, sigma; plain add outside the normalised tensors). g holds
+// gradients with respect to the effective parameters, which the workspace must hold for slot s (sn_enter)
+int sn_project(gi_net* net, int s, const float* g, float* dst, int64_t lo, int64_t hi, const float* scale_dev) {
+  SnSegs S = sn_segs(net, s, lo, hi);
+  SnJobs P;
+  const float* eff = (const float*)net->shared(net->oSnEff);
+  for (int t = 0; t < 6; ++t) {
+    const gi_net::SnTensor& T = net->snt[t];
+    if (T.off < lo || T.off >= hi) continue;
+    SnJob& J = P.j[P.n];
+    J.w = eff + T.off; J.g = g + T.off; J.ca = T.ca; J.K = T.K; J.cb = T.cb;
+    op_sn_carve(J, (float*)net->shared(T.scratch));
+    S.s[P.n].c = J.c;
+    ++P.n;
+  }
+  return op_sn_project_add(net->ctx->stream, P, S, g, dst, lo, hi, scale_dev);
+}
 
 // [rows][b] -> [rows][bp] zero-padded (the outermost up-convolution of a multi-channel generator)
 __global__ void __launch_bounds__(256) pad_b_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t rows, int b, int bp) {
@@ -611,14 +727,11 @@ extern "C" int gi_net_sync_weights(gi_net* net) {
   GI_REQUIRE(net && net->bound, "sync_weights: net not bound");
   if (net->kind == 2) return gi_dcgan_sync(net->dc, net->ctx->stream, net->params, net->ws);
   ++net->affine_gen;   // parameters (and possibly running statistics) were written from outside
+  // spectral norm: the packed copies derive from the effective weights, which every forward re-derives (patchgan_forward)
+  if (net->sn) { net->sn_eff_gen = 0; return GI_OK; }
   PackJobs P;
   P.n = 0;
-  auto add = [&](const Conv& c) {
-    PackJob& J = P.j[P.n++];
-    J.w = net->params + c.w_off; J.ca = c.ca; J.cb = c.cb; J.tile0 = 0; J.scale_on_b = 0; J.scale = nullptr;
-    J.packed = c.packed_off >= 0 ? (void*)net->shared(c.packed_off) : nullptr;
-    J.phase = net->shared(c.phase_off);
-  };
+  auto add = [&](const Conv& c) { pack_job(net, c, P); };
   if (net->kind == 0) {
     for (int k = 2; k <= net->nd; ++k) {
       if (P.n + 2 > 16) { GI_TRY(op_pack_weights_batch(net->ctx->stream, net->dtype, P)); P.n = 0; }
@@ -1654,6 +1767,8 @@ int patchgan_forward(gi_net* net, int s, const float* x, float* y, int n) {
   net->slot_train[s] = train;
   const bool fuse_a4 = net->fuse_head && op_head_affine_ok(dt, 512);
   net->slot_fused_u2[s] = fuse_a4 ? 1 : 0;   // (critic: "conv4's activation was not materialised")
+  ParamsBack params_back{net, net->params};
+  if (net->sn) GI_TRY(sn_enter(net, s, true));
   GI_TRY(op_c1_gather(st, dt, x, net->params + net->dconv[1].w_off, net->slot(s, net->oA[1]), n, H / 2, W / 2, 64, 64, 0, GI_ACT_LRELU, 1.f, nullptr,
                       gi_opt(GI_OPT_MASK_BITS) ? (unsigned long long*)net->slot(s, net->oBits1) : nullptr, &net->slot_bits1[s]));
   bool x_saved = false, a4_deferred = false;
@@ -1805,8 +1920,11 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
   float* th = (float*)net->shared(net->oTh);
   float* dth = th + (int64_t)n * net->P;
   float* ytmp = sumsq;   // (n) critic outputs, overwritten by sumsq afterwards
-  // 1) primal forward + frozen backward: g = d(sum D)/dx
+  // 1) primal forward + frozen backward: g = d(sum D)/dx. Spectral norm: this forward runs its own power iteration, and every pass
+  // below reads the effective parameters it derived
+  ParamsBack params_back{net, net->params};
   GI_TRY(patchgan_forward(net, s, xhat, ytmp, n));
+  if (net->sn) GI_TRY(sn_enter(net, s, false));
   GI_REQUIRE(!net->slot_fused_u2[s], "internal: gradient_penalty needs conv4's activation materialised");
   hipLaunchKernelGGL(fill_f32_kernel, dim3(1), dim3(256), 0, st, ones, n, 1.0f);
   GI_LAUNCH_CHECK();
@@ -1888,7 +2006,8 @@ int patchgan_gradient_penalty(gi_net* net, const float* xhat, int n, float lam, 
     GI_TRY(op_c1_wgrad(st, dt, D2 + half, (const float*)net->slot(s, net->oX), net->grads + net->dconv[1].w_off, n, H / 2, W / 2, 64, 64, 0, 0,
                        iLS, 1.f, nullptr, (float*)net->shared(net->oPart), net->part_floats));
   }
-  // 5) bound gradients += private buffer * 1/s
+  // 5) bound gradients += private buffer * 1/s (spectral norm: projected through this forward's u, v, sigma on the way)
+  if (net->sn) return sn_project(net, s, gbuf, grads, 0, net->n_params, sc + 1);
   GI_TRY(op_gp_unscale_add(st, gbuf, sc, grads, net->n_params));
   return GI_OK;
 }
@@ -2027,10 +2146,45 @@ extern "C" int gi_patchgan_gp_saved_activation(gi_net* net, int level, float* ou
   return saved_activation(net, net->gp_slot, 0, level, out_nchw, count);
 }
 
+extern "C" int gi_net_sn_read(gi_net* net, int slot, float* sigma6, float* eff_params, int64_t count) {
+  GI_REQUIRE(net && net->bound && net->kind == 1 && net->sn, "sn_read: bound discriminator handle with spectral norm required");
+  GI_REQUIRE(slot >= 0 && slot <= net->n_slots && net->slot_sn_gen[slot] > 0, "sn_read: slot %d holds no forward", slot);
+  hipStream_t st = net->ctx->stream;
+  if (sigma6) GI_HIP(hipMemcpyAsync(sigma6, sn_slot_sigma(net, slot), 6 * 4, hipMemcpyDeviceToDevice, st));
+  if (eff_params) {
+    GI_REQUIRE(count == net->n_params, "sn_read: count %lld != %lld parameter floats", (long long)count, (long long)net->n_params);
+    GI_REQUIRE(net->sn_eff_gen == net->slot_sn_gen[slot], "sn_read: the effective parameters in the workspace belong to another forward");
+    GI_HIP(hipMemcpyAsync(eff_params, net->shared(net->oSnEff), (size_t)count * 4, hipMemcpyDeviceToDevice, st));
+  }
+  return GI_OK;
+}
+
+// backward_joined for a critic with spectral norm whose slot holds a forward
+static int backward_joined_sn(gi_net* net, int slot, const float* dy, float* dx, int need_wgrad, int phase) {
+  ParamsBack params_back{net, net->params};
+  struct GradsBack { gi_net* net; float* g; ~GradsBack() { net->grads = g; } } grads_back{net, net->grads};
+  const int64_t split = net->dconv[4].w_off, lo = phase == 1 ? split : 0, hi = phase == 2 ? split : net->n_params;
+  GI_TRY(sn_enter(net, slot, false));
+  if (need_wgrad) {
+    float* priv = (float*)net->shared(net->oSnGrad);
+    GI_HIP(hipMemsetAsync(priv + lo, 0, (size_t)(hi - lo) * 4, net->ctx->stream));
+    net->grads = priv;
+  }
+  GI_TRY(side_begin(net, need_wgrad));
+  const int rc = patchgan_backward(net, slot, dy, dx, need_wgrad, phase);
+  const int rj = side_join(net);
+  if (rc != GI_OK || rj != GI_OK) return rc != GI_OK ? rc : rj;
+  if (need_wgrad) return sn_project(net, slot, net->grads, grads_back.g, lo, hi, nullptr);
+  return GI_OK;
+}
+
 // weight gradients on the second stream (side_begin), joined before the caller sees the gradients
 static int backward_joined(gi_net* net, int slot, const float* dy, float* dx, int need_wgrad, int phase) {
   if (net->kind == 2)
     return gi_dcgan_backward(net->dc, net->ctx->stream, net->params, net->grads, net->ws, slot, dy, dx, need_wgrad, net->loss_scale, phase);
+  // spectral norm: the backward differentiates the forward's effective weights (re-derived from the slot's sigma when a later
+  // forward has replaced them) into the private buffer; after the join the projection folds that into the bound gradients
+  if (net->sn && net->slot_n[slot] > 0) return backward_joined_sn(net, slot, dy, dx, need_wgrad, phase);
   GI_TRY(side_begin(net, need_wgrad));
   const int rc = net->kind == 0 ? unet_backward(net, slot, dy, dx, need_wgrad, phase) : patchgan_backward(net, slot, dy, dx, need_wgrad, phase);
   const int rj = side_join(net);

@@ -56,10 +56,14 @@ def setup(state, title):
 def build_networks(state, device, n_disc=1, sigmoid=True):
     """The generator and n_disc discriminators of a plugin. -d chooses the discriminator of the minimax plugins
     (minimaxgan_*, experiment1_global_local_D: PatchGAN or DCGAN); the WGAN plugins (sigmoid=False) always build a
-    PatchGAN critic, as the reference hard-codes it (wgan_l1.py:58)."""
+    PatchGAN critic, as the reference hard-codes it (wgan_l1.py:58). state['spectral_norm'] / state['sn_iterations']
+    (train.py --spectral-norm, --sn-iterations): every PatchGAN built here is spectrally normalised."""
     size = state["imagedim"]
     dtype = state.get("dtype", "fp16")
     disc = state.get("discriminator", "patchgan")
+    sn = dict(spectral_norm=True, n_power_iterations=int(state.get("sn_iterations") or 1)) if state.get("spectral_norm") else {}
+    if sn and disc == "dcgan":
+        raise ValueError("--spectral-norm normalises the PatchGAN critic only: it cannot be combined with -d dcgan")
     if state.get("generator", "unet") != "unet" or disc not in ("patchgan", "dcgan"):
         raise NotImplementedError("HIP backend accelerates -g unet with -d patchgan or -d dcgan (train.py:27-28)")
     if disc == "dcgan" and not sigmoid:
@@ -77,7 +81,8 @@ def build_networks(state, device, n_disc=1, sigmoid=True):
     if disc == "dcgan":   # experiment1_global_local_D: global and local discriminator both (reference :115-116)
         Ds = [networks.DCGANDiscriminator(dtype=dtype).to(device) for _ in range(n_disc)]
     else:
-        Ds = [networks.PatchGANDiscriminator(sigmoid=sigmoid, image_size=size, dtype=dtype).to(device) for _ in range(n_disc)]
+        Ds = [networks.get_network("discriminator", "patchgan", sigmoid=sigmoid, image_size=size, dtype=dtype, **sn).to(device)
+              for _ in range(n_disc)]
     return G.to(device), Ds
 
 

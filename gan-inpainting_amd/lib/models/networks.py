@@ -692,45 +692,103 @@ class Flatten(nn.Module):
 
 class PatchGANDiscriminator(HipNet):
     """networks.py:331-363. `image_size` generalises the hard-coded Linear(25,1) (valid for
-    128x128 only) to Linear((H/16-3)*(W/16-3), 1); n_d_channel is ignored as in the reference."""
+    128x128 only) to Linear((H/16-3)*(W/16-3), 1); n_d_channel is ignored as in the reference.
 
-    def __init__(self, c=1, n_d_channel=64, sigmoid=True, image_size=128, dtype=None):
+    spectral_norm=True (not in the reference): the five convolution weights and the Linear weight are spectrally normalised
+    with the semantics of torch.nn.utils.spectral_norm (gi_patchgan_create_sn). The parameters are then named
+    `weight_orig`, with buffers `weight_u` / `weight_v`, so the state dict loads strictly into an nn.Sequential of the same
+    layers wrapped with torch.nn.utils.spectral_norm, and back. One forward call is one round of n_power_iterations: a
+    stacked [real | fake] forward runs one where two calls run two, and gradient_penalty runs one more."""
+
+    _SN_LAYERS = (0, 2, 5, 8, 11, 13)
+
+    def __init__(self, c=1, n_d_channel=64, sigmoid=True, image_size=128, dtype=None, spectral_norm=False,
+                 n_power_iterations=1):
         super().__init__(dtype)
         if c != 1:
             raise NotImplementedError("HIP backend: PatchGANDiscriminator is built for 1-channel images")
         self.sigmoid = bool(sigmoid)
         self.image_size = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size)
-        lib = B.lib()
+        self.spectral_norm = bool(spectral_norm)
+        self.n_power_iterations = int(n_power_iterations)
+        if self.spectral_norm and self.n_power_iterations < 1:
+            raise ValueError(f"n_power_iterations must be >= 1, got {n_power_iterations}")
+        self._wname = "weight_orig" if self.spectral_norm else "weight"
         h = C.c_void_p()
-        B.check(lib.gi_patchgan_create(None, self.image_size[0], self.image_size[1], int(self.sigmoid), 1, self._dtype, 1,
-                                       C.byref(h)))
+        lib = self._create(None, self.image_size[0], self.image_size[1], 1, 1, h)
         self._build_tree(self._inventory(h), lib.gi_net_param_floats(h), lib.gi_net_buffer_floats(h))
         lib.gi_net_destroy(h)
         self.always_sync = True   # 2.8 M params: re-deriving the packed copies costs microseconds and makes
         #                           raw `p.data.clamp_()` loops (wgan_l1.py:151-153) safe
         self.reset_parameters()
 
+    def _create(self, ctx, H, W, max_n, n_slots, h):
+        lib = B.lib()
+        if self.spectral_norm:
+            B.check(lib.gi_patchgan_create_sn(ctx, H, W, int(self.sigmoid), 1, self.n_power_iterations, max_n, self._dtype,
+                                              n_slots, C.byref(h)))
+        else:
+            B.check(lib.gi_patchgan_create(ctx, H, W, int(self.sigmoid), max_n, self._dtype, n_slots, C.byref(h)))
+        return lib
+
+    def _reset_uv(self, idx):
+        """u, v as torch.nn.utils.spectral_norm draws them: normalised randn from torch's generator, u first."""
+        if self.spectral_norm:
+            for leaf in ("weight_u", "weight_v"):
+                t = self._tensor(f"model.{idx}.{leaf}")
+                t.copy_(nn.functional.normalize(torch.empty(t.shape).normal_(0, 1), dim=0, eps=1e-12))
+
     def reset_parameters(self):
+        wn = self._wname
         with torch.no_grad():
             chans = [1, 64, 128, 256, 512]
             for i, idx in enumerate((0, 2, 5, 8)):
                 w, _ = _init_conv(chans[i + 1], chans[i])
-                self._tensor(f"model.{idx}.weight").copy_(w)
+                self._tensor(f"model.{idx}.{wn}").copy_(w)
+                self._reset_uv(idx)
             m = nn.Conv2d(512, 1, 4, 1, 0, bias=False)
-            self._tensor("model.11.weight").copy_(m.weight.detach())
-            lin = nn.Linear(self._tensor("model.13.weight").shape[1], 1)
-            self._tensor("model.13.weight").copy_(lin.weight.detach())
+            self._tensor(f"model.11.{wn}").copy_(m.weight.detach())
+            self._reset_uv(11)
+            lin = nn.Linear(self._tensor(f"model.13.{wn}").shape[1], 1)
+            self._tensor(f"model.13.{wn}").copy_(lin.weight.detach())
             self._tensor("model.13.bias").copy_(lin.bias.detach())
+            self._reset_uv(13)
             self._reset_batchnorm()
         self._dirty = True
 
     def _create_handle(self, ctx, H, W, max_n):
         if (H, W) != self.image_size:
             raise ValueError(f"PatchGANDiscriminator was built for {self.image_size} images (its Linear head has "
-                             f"{self._tensor('model.13.weight').shape[1]} inputs), got {(H, W)}")
+                             f"{self._tensor('model.13.' + self._wname).shape[1]} inputs), got {(H, W)}")
         h = C.c_void_p()
-        B.check(B.lib().gi_patchgan_create(ctx, H, W, int(self.sigmoid), max_n, self._dtype, self.n_slots, C.byref(h)))
+        self._create(ctx, H, W, max_n, self.n_slots, h)
         return h
+
+    def _sn_read(self, slot, want_eff):
+        if not self.spectral_norm:
+            raise B.BackendError("this critic was built without spectral_norm")
+        if self._handle is None:
+            raise B.BackendError("no forward has run on this critic yet")
+        slot = self._last_slot if slot is None else slot
+        sig = torch.empty(6, dtype=torch.float32, device=self.device)
+        eff = torch.empty(self._n_params, dtype=torch.float32, device=self.device) if want_eff else None
+        B.check(B.lib().gi_net_sn_read(self._handle, slot, B.ptr(sig), B.ptr(eff), self._n_params))
+        return sig, eff
+
+    def spectral_sigmas(self, slot=None):
+        """{layer: sigma} of the forward held in `slot` (default: the last forward; "gp": the last gradient penalty's own)."""
+        sig, _ = self._sn_read(self.n_slots if slot == "gp" else slot, False)
+        return {f"model.{idx}": v for idx, v in zip(self._SN_LAYERS, sig.tolist())}
+
+    def effective_parameters(self):
+        """{name: tensor} of the parameters the last forward computed with: weight_orig / sigma under the key `weight`
+        (logical shapes), the others as they are. Parity tests."""
+        _, eff = self._sn_read(None, True)
+        out = {}
+        for t in self._inv:
+            if t["kind"] <= 1:
+                out[t["name"].replace("weight_orig", "weight")] = self._view(eff, t).clone()
+        return out
 
     def _output_shape(self, n, H, W):
         return (n, 1)

@@ -117,6 +117,11 @@ def build_parser():
     parser.add_argument("--dtype", choices=["fp16", "fp32"], default="fp16")
     parser.add_argument("--gp-lambda", dest="gp_lambda", type=float, default=0.0,
                         help="> 0: WGAN-GP gradient penalty (extension) instead of the reference's weight clipping")
+    parser.add_argument("--spectral-norm", dest="spectral_norm", action="store_true", default=False,
+                        help="spectrally normalise the PatchGAN critic's convolution and Linear weights (torch.nn.utils.spectral_norm "
+                             "semantics, HIP kernels); every PatchGAN the experiment builds; not with -d dcgan")
+    parser.add_argument("--sn-iterations", dest="sn_iterations", type=int, default=1,
+                        help="power iterations per critic forward with --spectral-norm")
     parser.add_argument("--face-parsing", dest="face_parsing", choices=["off", "random"], default="off",
                         help="random: a randomly initialised frozen UnetGenerator(1,4,7,ngf=32) stands in for the reference's "
                              "_states/face_segmentation checkpoint (train.py:169-175), which is not available")
@@ -166,7 +171,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.spectral_norm and args.discriminator == "dcgan":
+        parser.error("--spectral-norm normalises the PatchGAN critic only: it cannot be combined with -d dcgan")
+    if args.sn_iterations < 1:
+        parser.error("--sn-iterations must be >= 1")
     state = vars(args)
 
     import gan_inpainting_amd  # noqa: F401

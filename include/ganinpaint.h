@@ -126,6 +126,26 @@ int gi_unet_create_padded(gi_ctx* ctx, int num_downs, int ngf, int ch1, int out_
 /* PatchGANDiscriminator(c=1, sigmoid): Linear(25,1) generalised to ((H/16-3)*(W/16-3),1). */
 int gi_patchgan_create(gi_ctx* ctx, int H, int W, int sigmoid, int max_n, int dtype, int n_slots,
                        gi_net** out);
+/* The same critic with SPECTRAL NORMALISATION (spectral_norm != 0; 0 is gi_patchgan_create) of the five convolution weights and
+ * the Linear weight, with the semantics of torch.nn.utils.spectral_norm (eps 1e-12). Each weight, viewed as the ca x K matrix
+ * W = weight.view(ca, -1), keeps persistent vectors u (ca) and v (K, torch's column order). A train-mode forward runs
+ * n_power_iterations (>= 1) times v = W^T u / max(|W^T u|, eps), u = W v / max(|W v|, eps) in place, an eval-mode forward none;
+ * both then use W / sigma, sigma = u . (W v). The backward treats u, v as constants and differentiates sigma through W:
+ * dL/dW = (G - <G, W/sigma>_F u v^T) / sigma, G the gradient with respect to W / sigma. BatchNorm parameters and the Linear
+ * bias are not normalised. Inventory: the six weights are named "<layer>.weight_orig", and "<layer>.weight_u" / ".weight_v"
+ * are kind-4 buffers behind the running statistics. All of it is fp32 whatever the compute type.
+ * One forward call is one power iteration round, so a stacked [real | fake] forward (gi_net_set_bn_groups 2) runs one where two
+ * separate calls run two; gi_patchgan_gradient_penalty runs one more for its own primal forward. Every backward (and the
+ * penalty) uses the u, v, sigma of ITS forward, kept per slot. CONTRACT: the caller does not write the parameters between a
+ * forward and its backward (as for the packed copies). gi_net_sync_weights on such a handle only marks the derived copies
+ * stale: every forward re-derives them. Without spectral norm nothing is allocated, launched or named differently. */
+int gi_patchgan_create_sn(gi_ctx* ctx, int H, int W, int sigmoid, int spectral_norm, int n_power_iterations, int max_n,
+                          int dtype, int n_slots, gi_net** out);
+/* Parity tests: the six sigma (model.0, 2, 5, 8, 11, 13) of the forward held in `slot` (0 .. n_slots - 1, or n_slots: the last
+ * gradient penalty's own forward) to sigma6, and the effective parameters in the workspace - the flat parameter buffer with
+ * the six weights divided by sigma, count = gi_net_param_floats() - to eff_params; fails when those belong to another forward
+ * than the slot's. Device pointers, either may be NULL. Asynchronous on the context's stream. */
+int gi_net_sn_read(gi_net* net, int slot, float* sigma6, float* eff_params, int64_t count);
 /* DCGANDiscriminator() (reference lib/models/networks.py:162-212; get_network('discriminator', 'dcgan'), :23-24):
  * 4 x [Conv2d 5x5 s1 p1 + bias, ReLU, MaxPool 2/2], Linear 36864 -> 4096 -> 512 -> 2 (ReLU between), Softmax over the
  * two logits, view(-1, 1): y is (2n, 1), row 2i + j = p_j of image i. H = W = 128 only (Linear 12's 36864 = 1024*6*6
@@ -146,8 +166,8 @@ int gi_net_destroy(gi_net* net);
 
 /* parameter / buffer inventory, in the reference's named_parameters() order, then buffers.
  * kind: 0 conv weight (shape [a,b,4,4], physical [a][ky][kx][b]), 1 bias / BN affine / Linear
- * (contiguous), 2 BN running_mean, 3 BN running_var. offset is in floats into the flat param
- * (kind 0,1) or flat buffer (kind 2,3) allocation. */
+ * (contiguous), 2 BN running_mean, 3 BN running_var, 4 plain buffer (spectral norm: weight_u, weight_v). offset is in
+ * floats into the flat param (kind 0,1) or flat buffer (kind 2,3,4) allocation. */
 int gi_net_tensor_count(gi_net* net);
 int gi_net_tensor_desc(gi_net* net, int index, char* name, int name_cap, int* kind, int64_t* shape4,
                        int* ndim, int64_t* offset, int64_t* numel);
@@ -681,6 +701,15 @@ int gi_debug_bn_tangent_inject(gi_ctx* ctx, int dtype, const void* dta, const vo
 int gi_debug_gp_direction(gi_ctx* ctx, const float* g, int n, int64_t hw, float lam, float* sumsq, float* amax, float* v,
                           float* penalty, float* sc);
 int gi_debug_gp_unscale_add(gi_ctx* ctx, const float* src, const float* sc, float* dst, int64_t count);
+/* Spectral normalisation, one op at a time (specnorm.hip), any ca >= 1, K >= 1. w: ca x K row-major; cb > 0: a 4x4 convolution
+ * weight in the master layout [a][ky][kx][b] (K = 16 cb) whose memory column kk * cb + b is column b * 16 + kk of v; cb = 0:
+ * plain row-major. train: `iters` rounds of the power iteration update u (ca) and v (K) in place; else they are only read.
+ * *sigma_out = u . (W v). All device pointers; synchronises the context's stream. */
+int gi_debug_sn_power_iteration(gi_ctx* ctx, const float* w, int ca, int K, int cb, float* u, float* v, int iters, int train,
+                                float* sigma_out);
+/* dst += scale * (g - <g, w_eff>_F u v^T) / sigma; scale = scale_dev ? *scale_dev : 1; sigma: one device float. */
+int gi_debug_sn_project_add(gi_ctx* ctx, const float* g, const float* w_eff, const float* u, const float* v, const float* sigma,
+                            int ca, int K, int cb, const float* scale_dev, float* dst);
 /* adds addends[row][c] (fp32, device) to quantity q of population `group` of an accumulator block, row r into replica r & (reps - 1),
  * one workgroup per row and one lane per channel as the producing kernels do */
 int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends,
