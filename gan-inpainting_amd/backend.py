@@ -127,6 +127,11 @@ PROTOTYPES = {
     "gi_resize_to_tensor": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gi_mask_generate": (_i, [_vp, _i, _u64, _vp, _i, _i, _i, _vp, _vp]),
     "gi_batch_gather": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _u64, _i, _vp]),
+    "gi_diffaug_params": (_i, [_vp, _i, _u64, _u64, _i, _i, _i, _vp]),
+    "gi_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "gi_diffaug_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "gi_diffaug_apply": (_i, [_vp, _i, _u64, _u64, _vp, _i, _i, _i, _vp]),
+    "gi_diffaug_apply_bwd": (_i, [_vp, _i, _u64, _u64, _vp, _i, _i, _i, _vp]),
     "gi_check_finite": (_i, [_vp, _vp, _i64, _vp]),
     "gi_check_finite_scan": (_i, [_vp, _vp, _i64, _vp]),
     "gi_check_finite_finish": (_i, [_vp, _vp]),

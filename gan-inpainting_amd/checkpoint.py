@@ -28,6 +28,10 @@ class CheckpointError(RuntimeError):
 def compat_args(state, world, nets):
     """{key: value} of MATCH_KEYS from a plugin's state, the world size, and every network's parameter count (nets: name -> network)."""
     out = {k: state.get(k, _DEFAULTS.get(k)) for k in MATCH_KEYS}
+    if state.get("diffaug"):      # only when the option is on: states written without it keep their keys
+        from .lib.models.augment import parse_policy
+        out["diffaug"] = int(parse_policy(state["diffaug"]))
+        out["diffaug_seed"] = int(state.get("diffaug_seed") or 0)
     out["world_size"] = int(world)
     for name, net in nets.items():
         out[f"params/{name}"] = int(sum(p.numel() for p in net.parameters()))

@@ -91,6 +91,7 @@ int gi_ctx_create(int device_id, void* hip_stream, gi_ctx** out) {
 int gi_ctx_destroy(gi_ctx* ctx) {
   if (ctx && ctx->tickets) (void)hipFree(ctx->tickets);
   if (ctx && ctx->absmean_partials) (void)hipFree(ctx->absmean_partials);
+  if (ctx && ctx->diffaug_partials) (void)hipFree(ctx->diffaug_partials);
   delete ctx;
   return GI_OK;
 }

@@ -197,6 +197,7 @@ struct gi_ctx {
   hipStream_t stream;
   unsigned* tickets = nullptr;   // IgemmArgs::tickets for the single-layer entry points (allocated on first use)
   double* absmean_partials = nullptr;   // gi_grad_absmean: per-slice partial sums of every segment (allocated on first use)
+  double* diffaug_partials = nullptr;   // diffaug.hip: the per-sample partial sums of a colour pass (allocated on first use)
 };
 
 static inline size_t gi_dtype_size(int dtype) { return dtype == GI_F16 ? 2 : 4; }

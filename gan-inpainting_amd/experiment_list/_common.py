@@ -150,6 +150,16 @@ def make_ema(state, net_G):
     return optim.EMA(net_G, decay) if decay > 0 else None
 
 
+def make_diffaug(state):
+    """lib.models.augment.DiffAugment of state['diffaug'] / state['diffaug_seed'] (train.py --diffaug, --diffaug-seed), else None.
+    Only the step object takes it: the evaluation passes, the averaged generator and FID never see an augmented image."""
+    policy = state.get("diffaug")
+    if not policy:
+        return None
+    from ..lib.models.augment import DiffAugment
+    return DiffAugment(policy, seed=int(state.get("diffaug_seed") or 0))
+
+
 def _rng_states(device):
     return {"torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(device)}
 
@@ -367,4 +377,4 @@ def make_sync():
     return None
 
 
-__all__ = ["setup", "build_networks", "run_epochs", "make_optimizers", "make_sync", "make_ema", "wgan_cadence", "trainer"]
+__all__ = ["setup", "build_networks", "run_epochs", "make_optimizers", "make_sync", "make_ema", "make_diffaug", "wgan_cadence", "trainer"]

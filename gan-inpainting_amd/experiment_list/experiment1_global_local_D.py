@@ -11,6 +11,8 @@ from ..lib import pytorch_ssim
 
 def begin(state, loaders):
     state, exp_dir, logger, device = C.setup(state, "experiment1_global_local_D")
+    if state.get("diffaug"):
+        raise ValueError("--diffaug is not defined for experiment1_global_local_D: its local critic looks at mask * x (DESIGN.md 4.8)")
     net_G, (net_Dg, net_Dl) = C.build_networks(state, device, n_disc=2, sigmoid=True)
     opt_G, opt_D = C.make_optimizers("adam", net_G, optim.chain(net_Dl.parameters(), net_Dg.parameters()))   # :122-123
     step = C.trainer.DualDStep(net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=state.get("lambda1", 300.0),

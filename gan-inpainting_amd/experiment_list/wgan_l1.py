@@ -11,7 +11,8 @@ def begin(state, loaders):
     net_G, (net_D,) = C.build_networks(state, device, n_disc=1, sigmoid=False)    # wgan_l1.py:58
     opt_G, opt_D = C.make_optimizers("rmsprop", net_G, net_D.parameters())
     step = C.trainer.WGANStep(net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=C.make_sync(),
-                              gp_lambda=float(state.get("gp_lambda", 0.0)), overlap=bool(state.get("overlap", True)))   # > 0: WGAN-GP extension instead of clipping
+                              gp_lambda=float(state.get("gp_lambda", 0.0)), overlap=bool(state.get("overlap", True)),   # > 0: WGAN-GP extension instead of clipping
+                              diffaug=C.make_diffaug(state))
     step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 

@@ -37,7 +37,8 @@ def begin(state, loaders):
                     "reference, which evaluates them under no_grad; the fp16 range of the published VGG-19 weights is unchecked")
     pgrad = pgrad and vgg is not None
     step = C.trainer.WGANPerceptualStep(net_G, net_D, opt_G, opt_D, vgg=vgg, segment_model=seg, clip=0.01, sync=C.make_sync(),
-                                        overlap=bool(state.get("overlap", True)), perceptual_grad=pgrad)
+                                        overlap=bool(state.get("overlap", True)), perceptual_grad=pgrad,
+                                        diffaug=C.make_diffaug(state))
     step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 

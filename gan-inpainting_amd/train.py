@@ -96,6 +96,14 @@ class _Parser(argparse.ArgumentParser):
             self.error("--state-every must be > 0")
         if not 0.0 <= a.ema_decay < 1.0:
             self.error("--ema-decay takes 0 <= D < 1 (0 = off)")
+        if a.diffaug is not None:
+            names = [s.strip() for s in a.diffaug.split(",")]
+            if not all(n in ("color", "translation", "cutout") for n in names):
+                self.error(f"--diffaug takes a comma-separated, non-empty subset of color,translation,cutout (got {a.diffaug!r})")
+            if "experiment1_global_local_D" in a.experiments:
+                self.error("--diffaug is not defined for experiment1_global_local_D (its local critic looks at mask * x)")
+        elif a.diffaug_seed:
+            self.error("--diffaug-seed needs --diffaug")
         if a.resume not in ("", "auto") and len(a.experiments) > 1:
             self.error("--resume PATH names one experiment's state: give one -exp, or --resume auto")
         return a
@@ -164,6 +172,12 @@ def build_parser():
                              "a fresh start when it does not, so the same command line can be submitted again and again. The resumed "
                              "run equals the uninterrupted one bit for bit; -ep, --saveevery, --evalevery, --outdir, --workers and "
                              "--cache may differ, but changing --cache changes the batch order and ends that promise")
+    parser.add_argument("--diffaug", default=None, metavar="POLICY",
+                        help="differentiable augmentation of every image the critic sees, real and generated (Zhao et al. 2020; departs "
+                             "from the reference): any comma-separated subset of color,translation,cutout, drawn per sample on the "
+                             "device; the generator's gradient passes through the transform. Not for experiment1_global_local_D; "
+                             "evaluation, the averaged generator and FID never augment")
+    parser.add_argument("--diffaug-seed", dest="diffaug_seed", type=int, default=0, help="seed of the --diffaug draws")
     parser.add_argument("--ema-decay", dest="ema_decay", type=float, default=0.0,
                         help="> 0: keep an exponential moving average of the generator's weights (one HIP pass per generator update); "
                              "the evaluation pass adds train_ema / test_ema and epoch<N>_G_ema.pt is saved next to epoch<N>_G.pt")

@@ -90,8 +90,15 @@ class _StepBase:
     recon_weight = 1.0      # largest multiplier on a mean-reduced reconstruction loss (lambda)
     auto_loss_scale = True  # fp16 only: pick per-network loss scales from the batch geometry
 
-    def __init__(self, net_G, nets_D, device, sync=None, ema_G=None):
+    def __init__(self, net_G, nets_D, device, sync=None, ema_G=None, diffaug=None):
         self.G, self.Ds = net_G, list(nets_D)
+        # differentiable augmentation of everything a discriminator sees (lib/models/augment.py): None, a policy
+        # string or a DiffAugment. _aug_step counts the batches this object has processed: it keys the draws
+        if diffaug is not None and not hasattr(diffaug, "into"):
+            from .lib.models.augment import DiffAugment
+            diffaug = DiffAugment(diffaug)
+        self.aug = diffaug
+        self._aug_step = 0
         # optim.EMA of the generator (or None): updated right after every generator update, on its stream. It may also be set
         # after construction, which under data parallelism is after the parameter broadcast below
         self.ema_G = ema_G
@@ -125,6 +132,8 @@ class _StepBase:
             n, _, h, w = ground.shape
             # prediction / its gradient as the discriminator returns it: (n, 1), or (2n, 1) for DCGANDiscriminator
             self.dpred = torch.empty(self.Ds[0]._output_shape(n, h, w), dtype=torch.float32, device=ground.device)
+            if self.aug is not None:    # T(real) / T(generated) of the un-stacked critic calls, T2(inpainted) of the generator update
+                self.aug_a, self.aug_b = mk(), mk()
             self.L = {}
             if self.auto_loss_scale:
                 self._pick_loss_scales(ground)
@@ -182,10 +191,32 @@ class _StepBase:
         self._loaded_L = None
 
     def _extra_state(self):
-        return {}
+        return {} if self.aug is None else {"diffaug_step": int(self._aug_step)}
 
     def _load_extra_state(self, d):
-        pass
+        if self.aug is not None and "diffaug_step" in d:
+            self._aug_step = int(d["diffaug_step"])
+
+    # ---- differentiable augmentation: key = ((step * 4 + call) << 32) | (rank * n + row) ----
+    def _aug_into(self, x, call, out):
+        """out = T_call(x) with this batch's draws, on the current stream."""
+        n = x.shape[0]
+        self.aug.into(x, out, self._aug_step, call, (self.sync.rank if self.sync is not None else 0) * n)
+        return out
+
+    def _aug_adjoint(self, dy, call, out):
+        n = dy.shape[0]
+        self.aug.adjoint_into(dy, out, self._aug_step, call, (self.sync.rank if self.sync is not None else 0) * n)
+        return out
+
+    def _d_for_g(self, net, inp, kind, target, name, gscale=1.0):
+        """The generator update's critic call: loss into L[name], returns d(loss)/d(inp). With augmentation the critic sees
+        T2(inp) and its input gradient goes back through the adjoint."""
+        x = inp if self.aug is None else self._aug_into(inp, 2, self.aug_a)
+        p, t = self._fwd(net, x)
+        self.ops.adv(p, kind, target, self._loss(name), self.dpred, gscale)
+        d = self._bwd(net, t, self.dpred, True, False)
+        return d if self.aug is None else self._aug_adjoint(d, 2, self.g_adv)
 
     def _step_G(self, opt):
         """_step of the generator's optimizer, then the moving average of its parameters (same stream, no synchronisation)."""
@@ -274,10 +305,16 @@ class _StepBase:
         own, dp2 = bufs[key]
         if x2 is None:
             x2 = own
-        if not real_done:                             # (the caller may have copied the real half already, ahead of a wait)
-            x2[:n].copy_(real)
-        if fake.data_ptr() != x2[n:].data_ptr():      # the caller may have produced `fake` in the pair buffer already
-            x2[n:].copy_(fake)
+        if self.aug is not None:                      # T0(real) | T1(fake), written straight into the pair buffer
+            if not real_done:
+                self._aug_into(real, 0, x2[:n])
+            self._aug_into(fake, 1, x2[n:])
+        else:
+            if not real_done:                             # (the caller may have copied the real half already, ahead of a wait)
+                x2[:n].copy_(real)
+            if fake.data_ptr() != x2[n:].data_ptr():      # the caller may have produced `fake` in the pair buffer already
+                x2[n:].copy_(fake)
+        self._pair = x2
         p, t = self._fwd(net, x2, bn_groups=2)
         o.adv_pair(p, p.shape[0] // 2, kind, t_real, t_fake, self._loss(name_real), self._loss(name_fake), dp2, gs_real, gs_fake)
         if synced:
@@ -313,8 +350,8 @@ class _StepBase:
 
 
 class MinimaxStep(_StepBase):
-    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True, ema_G=None):
-        super().__init__(net_G, [net_D], net_G.device, sync, ema_G)
+    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True, ema_G=None, diffaug=None):
+        super().__init__(net_G, [net_D], net_G.device, sync, ema_G, diffaug)
         self.D, self.optG, self.optD, self.recon = net_D, opt_G, opt_D, recon
         self.stacked = stacked      # D(ground) | D(inpainted) as one batch with per-half BatchNorm (see _d_pair)
         self._bind_optimizers(opt_G, opt_D)
@@ -331,24 +368,26 @@ class MinimaxStep(_StepBase):
         if self.stacked:
             self._d_pair(self.D, ground, self.inpainted, BCE, 1.0, 0.0, "d_loss_real", "d_loss_fake")
         else:
-            p, t = self._fwd(self.D, ground)
+            real, fake = ground, self.inpainted
+            if self.aug is not None:
+                real, fake = self._aug_into(ground, 0, self.aug_a), self._aug_into(self.inpainted, 1, self.aug_b)
+            p, t = self._fwd(self.D, real)
             o.adv(p, BCE, 1.0, self._loss("d_loss_real"), self.dpred)
             self._bwd(self.D, t, self.dpred, False, True)
-            p, t = self._fwd(self.D, self.inpainted)
+            p, t = self._fwd(self.D, fake)
             o.adv(p, BCE, 0.0, self._loss("d_loss_fake"), self.dpred)
             self._bwd(self.D, t, self.dpred, False, True)
         self._reduce(self.D)
         self._step(self.optD)
         # ---- G step :154-173 (D frozen: input gradient only)
         self.optG.zero_grad()
-        p, t = self._fwd(self.D, self.inpainted)
-        o.adv(p, BCE, 1.0, self._loss("g_adv"), self.dpred)
-        d_adv = self._bwd(self.D, t, self.dpred, True, False)
+        d_adv = self._d_for_g(self.D, self.inpainted, BCE, 1.0, "g_adv")
         o.recon(self.recon, self.inpainted, ground, self._loss("recon"), self.g_rec)
         o.add(d_adv, self.g_rec, self.tmp1)
         o.mul(self.tmp1, self.mask_c, self.g_gen)                              # d(inpainted)/d(gen) = mask
         self._bwd_G(gtok, self.g_gen)
         self._step_G(self.optG)
+        self._aug_step += 1
         return self.L
 
 
@@ -357,8 +396,8 @@ class WGANStep(_StepBase):
     package's RMSprop its `clamp` is set so the clip is fused into the optimizer kernel."""
 
     def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=None, gp_lambda=0.0, overlap=False, stacked=True,
-                 ema_G=None):
-        super().__init__(net_G, [net_D], net_G.device, sync, ema_G)
+                 ema_G=None, diffaug=None):
+        super().__init__(net_G, [net_D], net_G.device, sync, ema_G, diffaug)
         self.D, self.optG, self.optD, self.recon, self.clip = net_D, opt_G, opt_D, recon, clip
         # stacked=True: the critic's two calls of a batch, D(ground) and D(inpainted) (wgan_l1.py:134-135), run as ONE
         # 2n batch with independent BatchNorm statistics per half (gi_net_set_bn_groups): same arithmetic per
@@ -373,6 +412,7 @@ class WGANStep(_StepBase):
             self._sD = torch.cuda.Stream(device=net_G.device)
             net_D._release_handle()          # the handle launches on the stream that is current when it is created
             self._inp2 = [None, None]
+            self._inp1 = [None, None]       # with augmentation: the plain composite (the pair buffer holds its transform)
             self._evD = [None, None]
             self._k = 0
         # True: `ground` / `mask` were produced before the previous step was issued (resident in HBM, the
@@ -401,6 +441,12 @@ class WGANStep(_StepBase):
             # [ground | inpainted] of the stacked critic pass: the composite writes its half in place
             self._inp2[k] = torch.empty((2 * ground.shape[0],) + tuple(ground.shape[1:]), dtype=ground.dtype, device=ground.device)
         inp = self._inp2[k][ground.shape[0]:]
+        if self.aug is not None:
+            # the pair buffer takes T0(ground) | T1(inpainted) on the side stream; the composite goes to a plain buffer, which the
+            # reconstruction terms, the caller (metrics) and the transforms read. Two of them for the same reason as the pair
+            if self._inp1[k] is None or self._inp1[k].shape != ground.shape:
+                self._inp1[k] = torch.empty_like(ground)
+            inp = self._inp1[k]
         # the side stream reads the caller's `ground` (critic real half, gradient penalty): tell the caching allocator,
         # or a per-batch `ground` freed by the caller could be handed to the next batch's H2D copy while the critic
         # still reads it (critic-only batches never make the main stream wait for the side stream)
@@ -418,29 +464,37 @@ class WGANStep(_StepBase):
             if not self.inputs_resident:
                 sD.wait_event(e0)
             self.optD.zero_grad()
+            gp_real, gp_fake = ground, inp
             if self.stacked:
-                self._inp2[k][:ground.shape[0]].copy_(ground)   # the real half of the pair: before the wait for the inpainted one
+                # the real half of the pair: before the wait for the inpainted one
+                if self.aug is not None:
+                    self._aug_into(ground, 0, self._inp2[k][:ground.shape[0]])
+                    gp_real, gp_fake = self._inp2[k][:ground.shape[0]], self._inp2[k][ground.shape[0]:]
+                else:
+                    self._inp2[k][:ground.shape[0]].copy_(ground)
                 sD.wait_event(e_inp)
                 self._critic_stacked(ground, inp, x2=self._inp2[k], real_done=True)
             else:
-                pr, tr = self._fwd(self.D, ground)
+                if self.aug is not None:
+                    gp_real = self._aug_into(ground, 0, self.aug_a)
+                pr, tr = self._fwd(self.D, gp_real)
                 o.adv(pr, MEAN, 0.0, self._loss("d_loss_real"), self.dpred, +1.0)
                 self._bwd(self.D, tr, self.dpred, False, True)
                 sD.wait_event(e_inp)
-                pf, tf = self._fwd(self.D, inp)
+                if self.aug is not None:
+                    gp_fake = self._aug_into(inp, 1, self.aug_b)
+                pf, tf = self._fwd(self.D, gp_fake)
                 o.adv(pf, MEAN, 0.0, self._loss("d_loss_fake"), self.dpred, -1.0)
                 self._bwd(self.D, tf, self.dpred, False, True)
-            if self.gp_lambda > 0:
-                self.L["gp"] = self.D.gradient_penalty(ground, inp, getattr(self, "gp_eps", None), self.gp_lambda).view(1)
+            if self.gp_lambda > 0:      # with augmentation: between the two augmented halves
+                self.L["gp"] = self.D.gradient_penalty(gp_real, gp_fake, getattr(self, "gp_eps", None), self.gp_lambda).view(1)
             if not self._d_synced:
                 self._reduce(self.D)
             self._step(self.optD)
             if self.clip > 0 and not self._fused_clip:
                 util.clamp_parameters(self.D, -self.clip, self.clip)
             if update_g:
-                p, t = self._fwd(self.D, inp)
-                o.adv(p, MEAN, 0.0, self._loss("g_adv"), self.dpred, +1.0)
-                d_adv = self._bwd(self.D, t, self.dpred, True, False)
+                d_adv = self._d_for_g(self.D, inp, MEAN, 0.0, "g_adv", +1.0)
             self._evD[k] = sD.record_event()
         if update_g:
             # before the wait - the main stream has nothing else to do while the critic runs: clearing the generator's gradients
@@ -453,6 +507,7 @@ class WGANStep(_StepBase):
             o.mul(self.tmp1, self.mask_c, self.g_gen)
             self._bwd_G(gtok, self.g_gen)
             self._step_G(self.optG)
+        self._aug_step += 1
         return self.L
 
     def side_stream(self):
@@ -476,17 +531,22 @@ class WGANStep(_StepBase):
         gen, gtok = self._fwd(self.G, self.masked)                              # every batch, :119
         o.composite(self.masked, gen, self.mask_c, self.inpainted)
         self.optD.zero_grad()
+        gp_real, gp_fake = ground, self.inpainted
         if self.stacked:
             self._critic_stacked(ground, self.inpainted)
+            if self.aug is not None:
+                gp_real, gp_fake = self._pair[:ground.shape[0]], self._pair[ground.shape[0]:]
         else:
-            pr, tr = self._fwd(self.D, ground)                                      # :134
-            pf, tf = self._fwd(self.D, self.inpainted)                              # :135
+            if self.aug is not None:
+                gp_real, gp_fake = self._aug_into(ground, 0, self.aug_a), self._aug_into(self.inpainted, 1, self.aug_b)
+            pr, tr = self._fwd(self.D, gp_real)                                     # :134
+            pf, tf = self._fwd(self.D, gp_fake)                                     # :135
             o.adv(pr, MEAN, 0.0, self._loss("d_loss_real"), self.dpred, +1.0)       # backward(one)  :137-138
             self._bwd(self.D, tr, self.dpred, False, True)
             o.adv(pf, MEAN, 0.0, self._loss("d_loss_fake"), self.dpred, -1.0)       # backward(mone) :140-141
             self._bwd(self.D, tf, self.dpred, False, True)
-        if self.gp_lambda > 0:
-            self.L["gp"] = self.D.gradient_penalty(ground, self.inpainted, getattr(self, "gp_eps", None), self.gp_lambda).view(1)
+        if self.gp_lambda > 0:      # with augmentation: between the two augmented halves
+            self.L["gp"] = self.D.gradient_penalty(gp_real, gp_fake, getattr(self, "gp_eps", None), self.gp_lambda).view(1)
         if not self._d_synced:
             self._reduce(self.D)
         self._step(self.optD)                                                   # :147
@@ -494,13 +554,12 @@ class WGANStep(_StepBase):
             util.clamp_parameters(self.D, -self.clip, self.clip)                # :151-153
         if update_g:                                                            # cadence :157-163 is the caller's
             self.optG.zero_grad()
-            p, t = self._fwd(self.D, self.inpainted)
-            o.adv(p, MEAN, 0.0, self._loss("g_adv"), self.dpred, +1.0)
-            d_adv = self._bwd(self.D, t, self.dpred, True, False)
+            d_adv = self._d_for_g(self.D, self.inpainted, MEAN, 0.0, "g_adv", +1.0)
             o.add(d_adv, self._g_losses(self.inpainted, ground), self.tmp1)
             o.mul(self.tmp1, self.mask_c, self.g_gen)
             self._bwd_G(gtok, self.g_gen)
             self._step_G(self.optG)
+        self._aug_step += 1
         return self.L
 
     def _critic_stacked(self, ground, inp, x2=None, real_done=False):
@@ -552,10 +611,11 @@ class WGANPerceptualStep(WGANStep):
 
     def _extra_state(self):
         # perceptual_grad on an fp16 generator: the loss scale was picked once from the first generator update's VGG gradient
-        return {"recon_weight": float(self.recon_weight),
-                "vgg_scaled_for": None if self._vgg_scaled_for is None else list(self._vgg_scaled_for)}
+        return dict(super()._extra_state(), recon_weight=float(self.recon_weight),
+                    vgg_scaled_for=None if self._vgg_scaled_for is None else list(self._vgg_scaled_for))
 
     def _load_extra_state(self, d):
+        super()._load_extra_state(d)
         if "recon_weight" in d:
             self.recon_weight = float(d["recon_weight"])
             self._vgg_scaled_for = None if d.get("vgg_scaled_for") is None else tuple(d["vgg_scaled_for"])
@@ -611,7 +671,10 @@ class DualDStep(_StepBase):
     """G step first, LSGAN losses, global + local (mask * x) discriminators, mask not ceil-ed,
     output not composited, one optimizer over both discriminators (:123)."""
 
-    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True, ema_G=None):
+    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True, ema_G=None, diffaug=None):
+        if diffaug is not None:
+            # the local critic looks at mask * x: whether it shares the global critic's transform is undecided (DESIGN 4.8)
+            raise B.BackendError("DualDStep does not support diffaug")
         super().__init__(net_G, [net_Dg, net_Dl], net_G.device, sync, ema_G)
         self.stacked = stacked      # each discriminator's real | fake calls as one batch with per-half BatchNorm
         self.Dg, self.Dl, self.optG, self.optD, self.lam1, self.lam2 = net_Dg, net_Dl, opt_G, opt_D, lam1, lam2

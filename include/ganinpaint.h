@@ -502,6 +502,28 @@ int gi_mask_generate(gi_ctx* ctx, int kind, uint64_t seed, const int64_t* keys_d
 int gi_batch_gather(gi_ctx* ctx, const uint8_t* store, int64_t n_store, int h, int w, const int64_t* rows_dev, int n,
                     const int64_t* flip_keys_dev, uint64_t flip_seed, int out_kind, void* out);
 
+/* ---- differentiable augmentation of the critic's inputs (NOT in the reference): per sample of a (n,1,H,W) fp32
+ *      batch, in this order, colour  v = c (x - m) + (m + b)  with m the sample's mean, an integer translation t = (ty, tx) with
+ *      zero fill, and a cutout window set to zero:  y[q] = v[q - t] if q - t is inside the image and q outside the window, else 0.
+ *      The adjoint is  dv[p] = dy[p + t] if p + t is inside the image and outside the window, else 0;  dx = c dv + (1 - c) mean(dv).
+ *      policy: bits 1 colour, 2 translation, 4 cutout (any non-empty subset). The parameters are draws of the mask generator's
+ *      scheme above with seed' = seed ^ 0x4449464641554721 and key_i = key0 + i for sample i:  b = (draw(0) >> 8) 2^-24 - 0.5,
+ *      c = 0.5 + (draw(1) >> 9) 2^-23,  ty = uni(2, -(H/8), H/8), tx = uni(3, -(W/8), W/8),  cy = uni(4, 0, H), cx = uni(5, 0, W);
+ *      the window is ch = H/2 by cw = W/2 from y0 = cy - ch/2, x0 = cx - cw/2 (integer divisions). A disabled operation leaves
+ *      b = 0, c = 1 / t = 0 / ch = cw = 0 and does not change the other operations' draws.
+ *      table: n rows of 8 32-bit words on the device, {b, c (fp32), ty, tx, y0, x0, ch, cw (int32)}, the window unclipped.
+ *      gi_diffaug_fwd / _bwd take a table (hand-written ones included) and `colour` (0: the values are moved bit for bit, b and c
+ *      are not read; else the fp32 arithmetic above, every operation rounded once, the means summed in fp64 in a fixed order:
+ *      deterministic, independent of n and of the sample's row). gi_diffaug_apply / _apply_bwd draw the parameters themselves
+ *      (no table launch): the production entries. x / y (dy / dx): n samples each, 4-byte aligned, not overlapping, any n-row
+ *      slices of larger buffers; W % 4 == 0 with 16-byte aligned buffers takes the 128-bit path. n > 0, H, W >= 1,
+ *      H * W < 2^31. Invalid arguments return GI_ERR_INVALID before anything is launched; asynchronous on the context's stream. */
+int gi_diffaug_params(gi_ctx* ctx, int policy, uint64_t seed, uint64_t key0, int n, int H, int W, void* table);
+int gi_diffaug_fwd(gi_ctx* ctx, const float* x, const void* table, int n, int H, int W, int colour, float* y);
+int gi_diffaug_bwd(gi_ctx* ctx, const float* dy, const void* table, int n, int H, int W, int colour, float* dx);
+int gi_diffaug_apply(gi_ctx* ctx, int policy, uint64_t seed, uint64_t key0, const float* x, int n, int H, int W, float* y);
+int gi_diffaug_apply_bwd(gi_ctx* ctx, int policy, uint64_t seed, uint64_t key0, const float* dy, int n, int H, int W, float* dx);
+
 /* ---- single-layer entry points (unit parity tests and kernel roofline measurements) -------- */
 /* out[n,y,x,a] = act( sum_{ky,kx,b} in[n,2y-1+ky,2x-1+kx,b] * w[a][ky][kx][b] ), NHWC, dtype T.
  * in: (n,H,W,cb) ld=ldin; out: (n,H/2,W/2,ca) ld=ldout. w_packed is T [ca][16*cb].
