@@ -121,6 +121,11 @@ PROTOTYPES = {
     "gi_fid_stats_acc_doubles": (_i64, [_i]),
     "gi_fid_stats_update": (_i, [_vp, _vp, _vp, _i, _i]),
     "gi_fid_stats_finish": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "gi_featmetrics_workspace_bytes": (_i64, [_i, _i64, _i64, _i]),
+    "gi_kid_subset_sums": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
+    "gi_feat_knn_radius": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
+    "gi_feat_manifold_members": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp]),
+    "gi_debug_feat_gram": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "gi_resize_output_size": (_i, [_i, _i, _i, _vp, _vp]),
     "gi_resize_table_bytes": (_i64, [_i, _i, _i, _i]),
     "gi_resize_build_tables": (_i, [_vp, _i, _i, _i, _i, _vp]),

@@ -138,6 +138,15 @@ def _fid_stats(state, mode):
     return (-1, -1) if st is None or isinstance(st, (int, float)) else st
 
 
+def _dist_kwargs(state, mode):
+    """The opt-in arguments of evaluate.calculate_metric for KID / precision / recall (train.py --dist-metrics); {} when off."""
+    names = state.get("dist_metric_names")
+    feats = state.get(mode + "_feats")
+    if not names or feats is None:
+        return {}
+    return {"real_features": feats, "dist_metrics": names, "dist_options": state.get("dist_options")}
+
+
 def _world():
     import torch.distributed as dist
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -322,7 +331,7 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
             else:                                                # minimaxgan_l1.py:235-240
                 rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
                                                          inception_model=state.get("inception_model"), epoch=epoch,
-                                                         prepare=eval_prepare(state, device, k, epoch))
+                                                         prepare=eval_prepare(state, device, k, epoch), **_dist_kwargs(state, k))
                             for k in ("train", "test") if loaders.get(k) is not None}
                 if ema is not None:                              # the same metrics of the averaged generator
                     with ema.applied():
@@ -330,7 +339,8 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                             if loaders.get(k) is not None:
                                 rec_eval[k + "_ema"] = evaluate.calculate_metric(
                                     device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
-                                    inception_model=state.get("inception_model"), epoch=epoch, prepare=eval_prepare(state, device, k, epoch))
+                                    inception_model=state.get("inception_model"), epoch=epoch, prepare=eval_prepare(state, device, k, epoch),
+                                    **_dist_kwargs(state, k))
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))
             if rank0:        # every rank holds the same replica: one writer

@@ -92,9 +92,10 @@ def quantize8(x):
 
 
 @torch.no_grad()
-def calculate_activation_statistics(images, model, batch_size=50, dims=2048, cuda=True, verbose=False, quantize=False):
+def calculate_activation_statistics(images, model, batch_size=50, dims=2048, cuda=True, verbose=False, quantize=False, store=None):
     """images: a (n,1|3,H,W) float tensor in [0,1], or an iterable of such tensors or of loader items whose first entry is
-    one. Returns (mu, sigma) in fp64 from the device statistic."""
+    one. Returns (mu, sigma) in fp64 from the device statistic. store (optional, lib.fid.dist_metrics.FeatureStore): is fed
+    the same feature batches, so the rows themselves outlive the sweep; (mu, sigma) are the same with and without it."""
     if dims != 2048:
         raise NotImplementedError("only the 2048-wide pool3 features are built (dims=%r)" % (dims,))
     dev = model.flat.device
@@ -106,7 +107,10 @@ def calculate_activation_statistics(images, model, batch_size=50, dims=2048, cud
         x = x.to(dev, non_blocking=True).float().contiguous()
         if quantize:
             x = quantize8(x)
-        stats.update(model.features(x))
+        feats = model.features(x)
+        stats.update(feats)
+        if store is not None:
+            store.update(feats)
     return stats.finish()
 
 

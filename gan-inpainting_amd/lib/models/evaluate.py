@@ -12,6 +12,8 @@ the pass feeds the composites the reference saves per image to the Inception han
 statistic; without them `fid` is -1, the reference's own "not computed" value (:160). The reference writes
 the composites as JPEG files and reads them back; here they keep the 8-bit truncation of
 `(x * 255).astype(uint8)` but skip the file round trip (and with it JPEG's lossy coding).
+Beside FID, opt-in (`dist_metrics`, `real_features`): the Kernel Inception Distance and improved precision / recall of the same
+composites' features against stored ground-truth features (lib.fid.dist_metrics; the reference has neither).
 Like the reference, calculate_metric does NOT switch the network to eval(): BatchNorm and Dropout run
 in whatever mode the caller left them (training mode in the plugins)."""
 import ctypes as C
@@ -49,17 +51,26 @@ class ReconMeter:
 
 @torch.no_grad()
 def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", inception_model=None, epoch=None,
-                     is_flip_mask=False, prepare=None, fid_capture=None):
+                     is_flip_mask=False, prepare=None, fid_capture=None, real_features=None, dist_metrics=(), dist_options=None):
     """evaluate.py:85-177. `loader` yields (input, mask, _) like the reference's datasets; `prepare` (optional)
     maps a loader item to a (n,1,h,w) float32 device tensor (the device Resize + ToTensor for decoded bytes).
-    `fid_capture` (optional dict, tests): receives the composites fed to Inception and the pass's (mu, sigma)."""
+    `fid_capture` (optional dict, tests): receives the composites fed to Inception and the pass's (mu, sigma).
+    `dist_metrics`: names of lib.fid.dist_metrics.NAMES; with an `inception_model` and `real_features` (a FeatureStore or a
+    (n,2048) device tensor of ground-truth features) the composites' features are kept as well (at most
+    dist_options["max_images"] rows) and the record gains `kid` and / or `precision`, `recall` (dist_options: kid_subsets,
+    kid_subset_size, pr_k, seed); fid_capture then also receives "features". Without them the record is what it always was."""
     lib = B.lib()
     meter = ReconMeter(device)
     fid_on = inception_model is not None and not _no_fid_stats(fid_stats)
-    stats = None
-    if fid_on:
+    dist_on = bool(dist_metrics) and inception_model is not None and real_features is not None
+    stats = store = None
+    if fid_on or dist_on:
         from ..fid import fid_score
+    if fid_on:
         stats = fid_score.FidStats(inception_model.flat.device, 2048)
+    if dist_on:
+        from ..fid import dist_metrics as dm
+        store = dm.FeatureStore(inception_model.flat.device, 2048, max_rows=(dist_options or {}).get("max_images"))
     for inp, mask, *_ in loader:
         if prepare is not None:
             inp, mask = prepare(inp), prepare(mask)     # images first: a prepare that generates masks sizes them like the batch's images
@@ -73,11 +84,15 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         out = net(masked)                                                            # :134
         out = out.detach().contiguous()
         meter.update(inp, out, m)                                                    # :135-143
-        if fid_on:
+        if fid_on or dist_on:
             comp = torch.empty_like(out)                                             # :136 out * m + masked
             B.check(lib.gi_mask_composite(B.get_ctx(out.device), B.ptr(masked), B.ptr(out), B.ptr(m), B.ptr(comp), out.numel()))
             comp = fid_score.quantize8(comp)                                         # :155-158 without the file
-            stats.update(inception_model.features(comp))
+            feats = inception_model.features(comp)
+            if fid_on:
+                stats.update(feats)
+            if dist_on:
+                store.update(feats)
             if fid_capture is not None:
                 fid_capture.setdefault("composites", []).append(comp.cpu())
     metric = meter.result()
@@ -88,6 +103,10 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         if fid_capture is not None:
             fid_capture.update(mu=mu, sigma=sigma)
     metric.update({"fid": fid, "epoch": epoch})
+    if dist_on:
+        metric.update(dm.evaluate(real_features, store, dist_metrics, dist_options))
+        if fid_capture is not None:
+            fid_capture["features"] = store.features()
     return metric
 
 

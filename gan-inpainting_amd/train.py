@@ -104,6 +104,14 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--diffaug is not defined for experiment1_global_local_D (its local critic looks at mask * x)")
         elif a.diffaug_seed:
             self.error("--diffaug-seed needs --diffaug")
+        if a.dist_metrics is not None:
+            names = [s.strip() for s in a.dist_metrics.split(",") if s.strip()]
+            if not names or len(set(names)) != len(names) or not all(n in ("kid", "pr") for n in names):
+                self.error(f"--dist-metrics takes a comma-separated, non-empty subset of kid,pr (got {a.dist_metrics!r})")
+            if not a.fid_weights:
+                self.error("--dist-metrics needs --fid-weights: KID and precision / recall are computed from the Inception features")
+            if a.kid_subsets < 1 or a.kid_subset_size < 2 or a.pr_k < 1 or a.dist_max_images < 2:
+                self.error("--kid-subsets >= 1, --kid-subset-size >= 2, --pr-k >= 1 and --dist-max-images >= 2")
         if a.resume not in ("", "auto") and len(a.experiments) > 1:
             self.error("--resume PATH names one experiment's state: give one -exp, or --resume auto")
         return a
@@ -141,6 +149,15 @@ def build_parser():
     parser.add_argument("--fid-weights", dest="fid_weights", default="",
                         help="local path of the published FID Inception state dict (pt_inception-2015-12-05-*.pth); enables FID in the "
                              "evaluation pass (train.py:154-180). Nothing is ever downloaded; without the flag fid stays -1")
+    parser.add_argument("--dist-metrics", dest="dist_metrics", default=None, metavar="NAMES",
+                        help="any comma-separated subset of kid,pr: the evaluation pass adds the Kernel Inception Distance (kid) and / or "
+                             "improved precision and recall (pr) of the composites' Inception features against the ground truths', "
+                             "computed on the device in fp64 (lib/fid/dist_metrics.py). Needs --fid-weights; every rank evaluates its shard")
+    parser.add_argument("--kid-subsets", dest="kid_subsets", type=int, default=100, help="KID: number of subsets")
+    parser.add_argument("--kid-subset-size", dest="kid_subset_size", type=int, default=1000, help="KID: rows per subset (at most)")
+    parser.add_argument("--pr-k", dest="pr_k", type=int, default=3, help="precision / recall: the k of the k-NN radii")
+    parser.add_argument("--dist-max-images", dest="dist_max_images", type=int, default=10000,
+                        help="--dist-metrics keeps at most this many feature rows per set (the first ones; precision / recall is O(n^2 d))")
     parser.add_argument("--data", default="synthetic")
     parser.add_argument("--masks", choices=["files", "rect", "freeform"], default="files",
                         help="files: the masks the data supplies (the mask_source files of --data <dir>; host rectangles for "
@@ -245,9 +262,18 @@ def main(argv=None):
         inception_model.load_state_dict(torch.load(args.fid_weights, map_location="cpu"))
         inception_model = inception_model.to(device).eval()
         print("Calculating FID statistics")
+        if args.dist_metrics:
+            from gan_inpainting_amd.lib.fid import dist_metrics
+            state["dist_metric_names"] = dist_metrics.parse_names(args.dist_metrics)
+            state["dist_options"] = {"kid_subsets": args.kid_subsets, "kid_subset_size": args.kid_subset_size, "pr_k": args.pr_k,
+                                     "max_images": args.dist_max_images, "seed": 0}
         for k in ("train", "test"):
             grounds = (to_device_images(item[0], device, state) for item in loaders[k])
-            state[k + "_fid"] = fid_score.calculate_activation_statistics(grounds, inception_model, quantize=True)
+            # --dist-metrics: the same sweep keeps the feature rows (no second Inception pass)
+            store = dist_metrics.FeatureStore(device, 2048, max_rows=args.dist_max_images) if args.dist_metrics else None
+            state[k + "_fid"] = fid_score.calculate_activation_statistics(grounds, inception_model, quantize=True, store=store)
+            if store is not None:
+                state[k + "_feats"] = store
         state["inception_model"] = inception_model
     for name in args.experiments:
         exp = importlib.import_module(f"gan_inpainting_amd.experiment_list.{name}")

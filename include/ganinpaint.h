@@ -464,6 +464,37 @@ int64_t gi_fid_stats_acc_doubles(int d);
 int gi_fid_stats_update(gi_ctx* ctx, double* acc, const float* feats, int n, int d);
 int gi_fid_stats_finish(gi_ctx* ctx, const double* acc, double* mu, double* sigma, int d);
 
+/* ---- distribution metrics on the pool3 features (csrc/featmetrics.hip): the sums of the Kernel Inception
+ *      Distance and the k-NN manifolds of improved precision / recall ------------------------------------------------
+ * All of it reduces a Gram matrix G[i][j] = sum_k A[ia[i]][k] * B[ib[j]][k] of fp32 feature rows (row stride d floats,
+ * 1 <= d <= 8192) that is computed in fp64 (v_mfma_f64_16x16x4_f64, 64 x 64 tiles, K in ascending groups of four) and
+ * never stored. An element's bits depend on its two feature rows only; every reduction has one fixed order; there
+ * are no float atomics: results are the same bits run to run and do not depend on how a call was chunked.
+ * Every pointer is device memory, index lists are int32. The entries TRUST the indices (0 <= index < rows of the
+ * matrix): the caller checks them on the host (lib/fid/dist_metrics.py does). Asynchronous on the context's stream.
+ * Workspace (8-byte aligned device memory, supplied by the caller), T(n) = ceil(n / 64):
+ *   GI_FEAT_WS_KID      n = m, count = n_subsets:  8 * 3 * n_subsets * T(m)^2 bytes   one partial sum per tile
+ *   GI_FEAT_WS_RADIUS   n, count = k:              8 * (n + n * T(n) * min(k, 64))    row norms + per-tile candidates
+ *   GI_FEAT_WS_MEMBERS  n = na, n2 = nb:           8 * (na + nb)                      row norms
+ * (-1 for arguments the entries would refuse). No n x n matrix is ever held. */
+#define GI_FEAT_WS_KID 0
+#define GI_FEAT_WS_RADIUS 1
+#define GI_FEAT_WS_MEMBERS 2
+int64_t gi_featmetrics_workspace_bytes(int op, int64_t n, int64_t n2, int count);
+/* ix, iy: [n_subsets][m] rows of X / Y. sums[s] = { sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i,j} k(x_i, y_j) },
+ * k(a, b) = (a.b / d + 1)^3 evaluated as t = G / (double)d + 1.0, t * t * t; the diagonal is skipped by position in the
+ * list (a row drawn twice still pairs with its copy). One launch sequence for all subsets. m >= 2, n_subsets <= 21845. */
+int gi_kid_subset_sums(gi_ctx* ctx, const float* X, const float* Y, const int* ix, const int* iy, int n_subsets, int m, int d,
+                       void* ws, int64_t ws_bytes, double* sums);
+/* radii[i] = the k-th smallest D_ij = max(0, |a_i|^2 + |a_j|^2 - 2 G_ij) over j != i (self excluded by index; duplicates of
+ * a row count as neighbours at their computed distance). 1 <= k < n. */
+int gi_feat_knn_radius(gi_ctx* ctx, const float* A, int n, int d, int k, void* ws, int64_t ws_bytes, double* radii);
+/* member[j] = 1 when D(a_i, b_j) <= radii[i] for some row i of A, else 0 (nb bytes); *count (device) = how many are 1. */
+int gi_feat_manifold_members(gi_ctx* ctx, const float* A, int na, const double* radii, const float* B, int nb, int d, void* ws,
+                             int64_t ws_bytes, uint8_t* member, int* count);
+/* test seam: the gathered Gram matrix itself, G (na, nb) fp64. ia / ib may be NULL (the identity). */
+int gi_debug_feat_gram(gi_ctx* ctx, const float* A, const int* ia, int na, const float* B, const int* ib, int nb, int d, double* G);
+
 /* ---- input transform: transforms.Resize(size) + ToTensor() of train.py:69-72 on decoded
  *      8-bit grey images (lib/data/dataset.py:6-12). Bit-exact restatement of Pillow's antialiased bilinear
  *      resampler (22-bit fixed point, horizontal pass first, uint8 intermediate), then /255. ------------- */
