@@ -315,7 +315,7 @@ int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, in
   return op_c1_head4_dgrad(ctx->stream, g, w, out, n, Hs, Ws, ldout, coffout);
 }
 
-// ---- the normalisation / activation-backward passes (elementwise.hip) on their own: what tests/test_norm_ops_gpu.py drives ------
+// ---- the normalisation / activation-backward passes (norm.hip, elementwise.hip) on their own: what tests/test_norm_ops_gpu.py drives ------
 namespace {
 inline int dbg_epc(int dtype) { return dtype == GI_F16 ? 8 : 4; }
 inline bool dbg_dtype_ok(int dtype) { return dtype == GI_F16 || dtype == GI_F32; }

@@ -1,4 +1,4 @@
-// BatchNorm from the exact accumulators (stat_acc.h): the pieces shared by the normalisation pass (elementwise.hip), the kernels that
+// BatchNorm from the exact accumulators (stat_acc.h): the pieces shared by the normalisation pass (norm.hip), the kernels that
 // apply the affine map themselves (c1.hip, head.hip) and the GEMM that normalises its own output (igemm7.hip, IgemmFold).
 #pragma once
 #include "common.h"

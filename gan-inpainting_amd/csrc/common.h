@@ -67,8 +67,9 @@ __device__ __forceinline__ void gi_with_act(int act, F&& f) {
   else f(std::integral_constant<int, GI_ACT_LRELU>{});
 }
 // the same for a launch-constant flag (statistics wanted, bias present): the accumulator loops drop the work of the unused side
+// (host side too: a launcher's flag as a template argument of its kernel, vec16.h)
 template <typename F>
-__device__ __forceinline__ void gi_with_bool(bool b, F&& f) {
+__host__ __device__ __forceinline__ void gi_with_bool(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
 }

@@ -517,7 +517,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) igemm7_kernel(KP7 p)
       const h8_t h = __builtin_bit_cast(h8_t, raw[k]);
       float v[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {        // bn_apply_kernel's arithmetic (elementwise.hip)
+      for (int e = 0; e < 8; ++e) {        // bn_apply_kernel's arithmetic (norm.hip)
         float t = fmaf((float)h[e], fsc[e], fsh[e]);
         if (p.fact == GI_ACT_RELU) t = t > 0.f ? t : 0.f;
         else if (p.fact == GI_ACT_LRELU) t = t > 0.f ? t : 0.2f * t;

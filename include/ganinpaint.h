@@ -669,7 +669,7 @@ int gi_c1_head4_forward(gi_ctx* ctx, const void* X, const float* w, const float*
 int gi_c1_head4_dgrad(gi_ctx* ctx, const float* g, const float* w, void* out, int n, int Hs, int Ws, int ldout,
                       int coffout);
 /* ---- the normalisation and activation-backward passes on their own (test seam) ---------------------------------------------
- * Each entry checks what the kernels assume and forwards to the pass of csrc/elementwise.hip that the networks call; nothing here is
+ * Each entry checks what the kernels assume and forwards to the pass of csrc/norm.hip or csrc/elementwise.hip that the networks call; nothing here is
  * on a training path. Tensors are NHWC of the compute type T (pixels x channels, row pitch ld, channel offset coff; both multiples of
  * the 16-byte chunk: 8 channels for fp16, 4 for fp32); vectors are fp32. c / chunk must be a power of two <= 256 except for the
  * InstanceNorm passes (any multiple of the chunk). tests/norm_ref.py restates every one of them in fp64.

@@ -1,4 +1,4 @@
-"""Plain fp64 restatement of the normalisation and activation-backward passes of csrc/elementwise.hip, written from the
+"""Plain fp64 restatement of the normalisation and activation-backward passes of csrc/norm.hip, written from the
 semantics csrc/common.h documents (the ActBnBwdArgs block, the BatchNorm2d / InstanceNorm2d rules), the fixed-point rules of
 csrc/stat_acc.h and the dropout hash of csrc/bn_acc.h. No kernel arithmetic is copied: no chunks, no partial rows, no fp32.
 tests/test_norm_ref_cpu.py proves it against torch in fp64; tests/test_norm_ops_gpu.py compares the kernels with it.

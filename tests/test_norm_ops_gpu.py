@@ -1,4 +1,4 @@
-"""GPU tier: the normalisation and activation-backward passes of csrc/elementwise.hip ONE OP AT A TIME through the gi_debug_*
+"""GPU tier: the normalisation and activation-backward passes of csrc/norm.hip ONE OP AT A TIME through the gi_debug_*
 seam, against the fp64 restatement of tests/norm_ref.py (proved against torch by tests/test_norm_ref_cpu.py), in both compute types.
 
   kinks    the backward ops take mean, invstd, scale and shift as inputs, so the test decides every activation input itself: x is
@@ -17,9 +17,18 @@ names the kernels op_act_bn_bwd launches for it (K.dispatch restates the dispatc
 Found by this file: with ONE sample per population (BatchNorm count 1, InstanceNorm on a 1 x 1 plane) the fp32 passes took
 E[x^2] - m^2 from an fp32-rounded square, so a "variance" of up to 6e-8 x^2 stood next to eps = 1e-5 and invstd was off by up to
 2 % (seven fp32 cases failed: test_col_stats_bn_finalize[*-1-fp32], test_instance_norm[1-*-fp32]). The passes now take the
-variance of a single sample as zero."""
+variance of a single sample as zero.
+
+Bit records: with GI_NORM_HASHES naming a file, every output that check / check_sum judge, and the outputs asserted with torch.equal
+(exact dgamma / dbeta, the zero_next words, the drawn dropout mask), is recorded there as key -> sha256 of its bytes. The key names
+the test function, the compute type, the case's own fields and the output - not the kernels that served it - so two builds of the
+library that compute the same thing give equal records (profiles/norm_ops_hashes_*.json: two such records, condensed by
+tools/condense_hashes.py)."""
 import ctypes as C
+import hashlib
+import json
 import math
+import os
 
 import pytest
 import torch
@@ -65,6 +74,27 @@ def _release_device_buffers():
     _KEEP.clear()
 
 
+HASH_OUT = os.environ.get("GI_NORM_HASHES", "")
+_TEST = {"name": "", "code": ""}
+
+
+@pytest.fixture(autouse=True)
+def _hash_context(request):
+    params = getattr(getattr(request.node, "callspec", None), "params", {})
+    _TEST["name"] = request.node.originalname
+    _TEST["code"] = {F16: "fp16", F32: "fp32"}.get(params.get("code"), "-")
+    yield
+
+
+def record_bits(key, got):
+    """GI_NORM_HASHES: key -> sha256 of the bytes of `got` as the device produced them"""
+    if HASH_OUT:
+        d = json.load(open(HASH_OUT)) if os.path.exists(HASH_OUT) else {}
+        t = got.detach().cpu().contiguous()
+        d[f"{_TEST['name']}|{_TEST['code']}|{key}"] = hashlib.sha256(t.view(torch.uint8).numpy().tobytes()).hexdigest()
+        json.dump(d, open(HASH_OUT, "w"), indent=0, sort_keys=True)
+
+
 def _dev(t, dtype=torch.float32):
     """a device copy that lives until the test ends: a temporary handed over as a bare pointer would return to the allocator at
     once and the next copy would land on it before the kernel has run"""
@@ -85,15 +115,18 @@ def _sync():
         pytest.exit(f"device error: {e}", returncode=3)
 
 
-def check(name, got, ref, tol):
+def check(name, got, ref, tol, key=None):
+    """key: the name of the output in the bit record, where `name` also says which kernels ran"""
+    record_bits(key or name, got)
     got, ref = got.detach().cpu().double(), ref.double()
     ok, msg = report(name, got, ref, tol)
     record("norm_ops " + name, float((got - ref).abs().max() / (ref.abs().max() + 1e-30)) / tol)
     assert ok, msg
 
 
-def check_sum(name, got, ref, abs_terms, tol=SUM_TOL):
+def check_sum(name, got, ref, abs_terms, tol=SUM_TOL, key=None):
     """per channel |got - ref| <= tol * sum|addends|"""
+    record_bits(key or name, got)
     got, ref = got.detach().cpu().double(), ref.double()
     ratio = ((got - ref).abs() / (abs_terms.double() + 1e-30)).max().item()
     print(f"{name}: max |err| / sum|terms| = {ratio:.3e} tol={tol:.1e}")
@@ -409,7 +442,8 @@ def _acc_case(x, c, groups, reps, seed, zero_next=False, out_stride=None):
     return b, (acc, keep, outs, rm, rv, zn), rs
 
 
-def _check_zero_next(zn, used):
+def _check_zero_next(zn, used, key):
+    record_bits(key + " zero_next", zn)
     z = zn.cpu()
     if used:
         assert not z[:300].any(), "zero_next was not cleared"
@@ -449,6 +483,7 @@ def test_bn_apply_acc(code, pixels, c, act, groups, reps, drop, side, zero_next)
         filled = torch.full((pixels * c,), 9, dtype=torch.uint8, device="cuda")
         _call(B.lib().gi_debug_fill_dropout(B.get_ctx(), B.ptr(filled), pixels * c, seed, p))
         _sync()
+        record_bits(name + " mask", md)
         assert torch.equal(md.view(-1), filled), "the mask drawn in the pass differs from gi_debug_fill_dropout's"
         nhost = min(pixels * c, 20000)
         assert torch.equal(filled[:nhost].cpu(), R.dropout_mask(seed, nhost, p)), "the device draw differs from the splitmix64 restatement"
@@ -457,7 +492,7 @@ def test_bn_apply_acc(code, pixels, c, act, groups, reps, drop, side, zero_next)
     check(name, y[:, coffy:coffy + c], ref, _tol(code))
     assert tail_untouched(y, c, coffy), "bn_apply_acc wrote outside its channels"
     _check_bn_vectors(name, outs, rm, rv, rs, c, out_stride)
-    _check_zero_next(zn, zero_next)
+    _check_zero_next(zn, zero_next, name)
     if side:
         assert torch.equal(dst[:side_chunks * 4], src[:side_chunks * 4]) and bool((dst[side_chunks * 4:] == 42).all()), "side copy"
 
@@ -524,7 +559,7 @@ def test_bn_finalize_acc(code):
     _call(B.lib().gi_debug_bn_finalize_acc(B.get_ctx(), c, C.byref(b)))
     _sync()
     _check_bn_vectors("bn_finalize_acc", outs, rm, rv, rs, c, c + 2)
-    _check_zero_next(zn, True)
+    _check_zero_next(zn, True, "bn_finalize_acc")
 
 
 # =================================================================================================================
@@ -560,13 +595,20 @@ class K:
         return f"{red}+sums+apply<bn=1,G{groups}>"
 
     def id(self):
-        s = f"{self.dispatch()}|p{self.pixels}|c{self.c}|{self.inp}|{ACT_NAME[self.act]}|sign={self.sign}"
+        return f"{self.dispatch()}|{self.fields()}"
+
+    def fields(self):
+        s = f"p{self.pixels}|c{self.c}|{self.inp}|{ACT_NAME[self.act]}|sign={self.sign}"
         for flag, text in ((self.bn == "eval", "eval"), (self.acc, f"reps{self.acc}"), (self.reduce_done, "reduce_done"),
                            (self.zero_next, "zero_next"), (self.drop, "drop"), (self.small is not None, f"SMALL={self.small}"),
                            (self.exact, "exact")):
             if flag:
                 s += "|" + text
         return s
+
+    def key(self):
+        """the case in the bit record: its own fields, not the kernels"""
+        return f"{self.fields()}|bn={self.bn}|groups={self.groups}"
 
 
 BWD_CASES = [
@@ -720,23 +762,25 @@ def test_act_bn_bwd(code, k):
     finally:
         if k.small is not None:
             B.set_option("GI_BN_BWD_SMALL", -1)
-    name = f"act_bn_bwd {k.id()}"
+    name, key = f"act_bn_bwd {k.id()}", f"act_bn_bwd {k.key()}"
     pre_g, pre_b, ils = d["pre_g"].double(), d["pre_b"].double(), d["ils"]
     if not has_bn:
         ref = d["dz"]
     else:
         ref, rb, rg, ab, ag = R.act_bn_bwd(d["dz"], d["x"], d["gamma"], list(d["mean"]), list(d["inv"]), groups, k.bn == "eval", sums_given)
-    check(name + " dx", dx, ref, _tol(code))
+    check(name + " dx", dx, ref, _tol(code), key + " dx")
     if k.bn == "train":
         if k.exact:
+            record_bits(key + " dbeta", dbeta), record_bits(key + " dgamma", dgamma)
             assert torch.equal(dbeta.cpu().double(), pre_b + ils * rb), name + ": dbeta is not the exact sum"
             assert torch.equal(dgamma.cpu().double(), pre_g + ils * rg), name + ": dgamma is not the exact sum"
         else:
-            check_sum(name + " dbeta", dbeta, pre_b + ils * rb, pre_b.abs() + ils * ab)
-            check_sum(name + " dgamma", dgamma, pre_g + ils * rg, pre_g.abs() + ils * ag)
+            check_sum(name + " dbeta", dbeta, pre_b + ils * rb, pre_b.abs() + ils * ab, key=key + " dbeta")
+            check_sum(name + " dgamma", dgamma, pre_g + ils * rg, pre_g.abs() + ils * ag, key=key + " dgamma")
     else:
+        record_bits(key + " dbeta", dbeta), record_bits(key + " dgamma", dgamma)
         assert torch.equal(dbeta.cpu().double(), pre_b) and torch.equal(dgamma.cpu().double(), pre_g), name + ": parameter gradients were touched"
-    _check_zero_next(zn, bool(k.zero_next and k.acc and k.bn == "train"))
+    _check_zero_next(zn, bool(k.zero_next and k.acc and k.bn == "train"), key)
 
 
 def test_act_bn_bwd_rejects_dropout_behind_lrelu():
