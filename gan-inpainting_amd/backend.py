@@ -132,6 +132,11 @@ PROTOTYPES = {
     "gi_resize_to_tensor": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gi_mask_generate": (_i, [_vp, _i, _u64, _vp, _i, _i, _i, _vp, _vp]),
     "gi_batch_gather": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _u64, _i, _vp]),
+    "gi_image_quantize": (_i, [_vp, _vp, _i64, _vp]),
+    "gi_panel_assemble": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gi_mask_bbox": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "gi_window_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gi_feather_paste": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "gi_diffaug_params": (_i, [_vp, _i, _u64, _u64, _i, _i, _i, _vp]),
     "gi_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "gi_diffaug_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

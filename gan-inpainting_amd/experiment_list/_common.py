@@ -147,6 +147,16 @@ def _dist_kwargs(state, mode):
     return {"real_features": feats, "dist_metrics": names, "dist_options": state.get("dist_options")}
 
 
+def _panel_kwargs(state, mode, epoch, rank0, suffix=""):
+    """The opt-in `panel` argument of evaluate.calculate_metric (train.py --sample-rows K): <outdir>/samples/<mode>_epoch<N>[_ema].png,
+    written by rank 0; {} when off."""
+    rows = int(state.get("sample_rows") or 0)
+    if rows <= 0 or not rank0:
+        return {}
+    outdir = state.get("outdir") or os.path.join(os.getcwd(), "runs")
+    return {"panel": (os.path.join(outdir, "samples", f"{mode}_epoch{epoch:04d}{suffix}.png"), rows, int(state.get("sample_gutter", 2)))}
+
+
 def _world():
     import torch.distributed as dist
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -331,7 +341,8 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
             else:                                                # minimaxgan_l1.py:235-240
                 rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
                                                          inception_model=state.get("inception_model"), epoch=epoch,
-                                                         prepare=eval_prepare(state, device, k, epoch), **_dist_kwargs(state, k))
+                                                         prepare=eval_prepare(state, device, k, epoch), **_dist_kwargs(state, k),
+                                                         **_panel_kwargs(state, k, epoch, rank0))
                             for k in ("train", "test") if loaders.get(k) is not None}
                 if ema is not None:                              # the same metrics of the averaged generator
                     with ema.applied():
@@ -340,7 +351,7 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                                 rec_eval[k + "_ema"] = evaluate.calculate_metric(
                                     device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
                                     inception_model=state.get("inception_model"), epoch=epoch, prepare=eval_prepare(state, device, k, epoch),
-                                    **_dist_kwargs(state, k))
+                                    **_dist_kwargs(state, k), **_panel_kwargs(state, k, epoch, rank0, "_ema"))
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))
             if rank0:        # every rank holds the same replica: one writer

@@ -1,0 +1,120 @@
+"""Inpaint a picture of any size with a trained generator (not in the reference, whose eval.py feeds whole images
+through the network at their stored size).
+
+One window per image: the hole's bounding box decides a square window around it (`plan_window`), the window is cropped, resized
+to the model's S x S with the training pipeline's own resampler, repaired, resized back and blended into a copy of the picture
+with a feathered weight (csrc/imageout.hip). Every step around the generator is exact integer or single-rounding arithmetic and
+restated in tests/imageout_ref.py. A nonzero mask byte is a hole (minimaxgan_l1.py:113-122)."""
+import math
+
+import torch
+
+from .. import backend as B
+from . import imageout
+
+
+def plan_window(H, W, bbox, S, context=2.0, feather=8):
+    """The (wy, wx, wh, ww) window of a (H, W) image for a hole with the inclusive bounding box (y0, x0, y1, x1): a square of side
+    max(S, ceil(context * m), m + 2 * (feather + 1)), m the box's longer side, clipped to the image and centred on the box as far
+    as the image allows. It contains the box and leaves feather + 1 pixels around it on every side that is not the image's own edge,
+    so the blend weight is zero on every interior window border. Pure host integers (context: a ratio of small integers in practice)."""
+    y0, x0, y1, x1 = (int(v) for v in bbox)
+    if not (0 <= y0 <= y1 < H and 0 <= x0 <= x1 < W):
+        raise ValueError(f"plan_window: box {(y0, x0, y1, x1)} is empty or outside the {H} x {W} image")
+    bh, bw = y1 - y0 + 1, x1 - x0 + 1
+    m = max(bh, bw)
+    side = max(int(S), math.ceil(context * m), m + 2 * (int(feather) + 1))
+    wh, ww = min(H, side), min(W, side)
+    cy, cx = (y0 + y1 + 1) // 2, (x0 + x1 + 1) // 2
+    wy = min(max(cy - wh // 2, 0), H - wh)
+    wx = min(max(cx - ww // 2, 0), W - ww)
+    return wy, wx, wh, ww
+
+
+class _Resizer:
+    """gi_resize_to_tensor for single (h, w) -> (oh, ow) uint8 images, the coefficient tables cached per geometry."""
+
+    def __init__(self):
+        self._tables = {}
+
+    def __call__(self, src, oh, ow, out_f32=None, out_u8=None):
+        h, w = src.shape
+        lib, ctx = B.lib(), B.get_ctx(src.device)
+        key = (h, w, oh, ow, src.device.index)
+        if key not in self._tables:
+            t = torch.empty(lib.gi_resize_table_bytes(h, w, oh, ow), dtype=torch.uint8, device=src.device)
+            B.check(lib.gi_resize_build_tables(ctx, h, w, oh, ow, B.ptr(t)))
+            self._tables[key] = t
+        tmp = torch.empty((h, ow), dtype=torch.uint8, device=src.device)
+        B.check(lib.gi_resize_to_tensor(ctx, B.ptr(self._tables[key]), B.ptr(src), 1, h, w, oh, ow, B.ptr(out_f32), B.ptr(out_u8), B.ptr(tmp)))
+
+
+class Inpainter:
+    """Inpainter(generator, imagedim=S)(images, masks): lists of (H_i, W_i) uint8 device tensors of any sizes -> the repaired uint8
+    images. The generator is put in eval() (BatchNorm on running statistics, folded into the convolutions; no dropout) and sees
+    up to `batch` windows per forward. An image with an empty mask comes back unchanged and costs no forward."""
+
+    def __init__(self, generator, imagedim=128, context=2.0, feather=8, batch=16):
+        if not 0 <= int(feather) <= imageout.MAX_FEATHER:
+            raise ValueError(f"feather = {feather} (0 .. {imageout.MAX_FEATHER})")
+        if context < 1.0 or batch < 1 or imagedim < 1:
+            raise ValueError("Inpainter: context >= 1, batch >= 1, imagedim >= 1")
+        self.net = generator.eval()
+        self.S, self.context, self.feather, self.batch = int(imagedim), float(context), int(feather), int(batch)
+        self.forward_calls = 0          # generator forwards so far
+        self.capture = None             # tests: a dict here receives the windows and what went through the generator
+        self._resize = _Resizer()
+        self._bufs = {}
+
+    def _batch_buffers(self, n, device):
+        """(ground, mask, ceil(mask), masked, composite) fp32 (batch,1,S,S), allocated once per device."""
+        if device not in self._bufs:
+            self._bufs[device] = tuple(torch.empty((self.batch, 1, self.S, self.S), dtype=torch.float32, device=device) for _ in range(5))
+        return tuple(b[:n] for b in self._bufs[device])
+
+    @torch.no_grad()
+    def __call__(self, images, masks):
+        if len(images) != len(masks):
+            raise ValueError(f"{len(images)} images, {len(masks)} masks")
+        jobs, results = [], []
+        for i, (img, mk) in enumerate(zip(images, masks)):
+            for t in (img, mk):
+                if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda:
+                    raise B.BackendError("Inpainter takes (H,W) uint8 tensors on the gfx950 device")
+            if img.shape != mk.shape or img.device != mk.device:
+                raise ValueError(f"image {tuple(img.shape)} on {img.device}, mask {tuple(mk.shape)} on {mk.device}: one shape, one device")
+            img, mk = img.contiguous(), mk.contiguous()
+            H, W = img.shape
+            box = imageout.mask_bbox(mk)[0].tolist()       # the one device -> host copy per image
+            if box[2] < 0:
+                results.append(img)                        # nothing to repair
+                continue
+            results.append(None)
+            jobs.append((i, img, mk, plan_window(H, W, box, self.S, self.context, self.feather)))
+        if self.capture is not None:
+            self.capture.update(windows=[j[3] for j in jobs], masked=[], mask=[], output=[])
+        for k in range(0, len(jobs), self.batch):
+            self._run(jobs[k:k + self.batch], results)
+        return results
+
+    def _run(self, jobs, results):
+        lib, S, n = B.lib(), self.S, len(jobs)
+        dev = jobs[0][1].device
+        ctx = B.get_ctx(dev)
+        ground, mask, m, masked, comp = self._batch_buffers(n, dev)
+        for k, (_, img, mk, win) in enumerate(jobs):
+            self._resize(imageout.window_crop(img, win), S, S, out_f32=ground[k])                       # ToTensor: / 255
+            self._resize(imageout.window_crop(mk, win, binarize=True), S, S, out_f32=mask[k])
+        B.check(lib.gi_mask_apply(ctx, B.ptr(ground), B.ptr(mask), B.ptr(m), B.ptr(masked), ground.numel(), 1))   # ceil, as the plugins do
+        out = self.net(masked).contiguous()
+        self.forward_calls += 1
+        B.check(lib.gi_mask_composite(ctx, B.ptr(masked), B.ptr(out), B.ptr(m), B.ptr(comp), comp.numel()))
+        patch_s = imageout.quantize(comp)
+        for k, (i, img, mk, win) in enumerate(jobs):
+            patch = torch.empty((win[2], win[3]), dtype=torch.uint8, device=dev)
+            self._resize(patch_s[k, 0], win[2], win[3], out_u8=patch)
+            results[i] = imageout.feather_paste(img, mk, win, patch, self.feather)
+        if self.capture is not None:
+            self.capture["masked"].append(masked.clone())
+            self.capture["mask"].append(m.clone())
+            self.capture["output"].append(out)

@@ -51,14 +51,18 @@ class ReconMeter:
 
 @torch.no_grad()
 def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", inception_model=None, epoch=None,
-                     is_flip_mask=False, prepare=None, fid_capture=None, real_features=None, dist_metrics=(), dist_options=None):
+                     is_flip_mask=False, prepare=None, fid_capture=None, real_features=None, dist_metrics=(), dist_options=None,
+                     panel=None):
     """evaluate.py:85-177. `loader` yields (input, mask, _) like the reference's datasets; `prepare` (optional)
     maps a loader item to a (n,1,h,w) float32 device tensor (the device Resize + ToTensor for decoded bytes).
     `fid_capture` (optional dict, tests): receives the composites fed to Inception and the pass's (mu, sigma).
     `dist_metrics`: names of lib.fid.dist_metrics.NAMES; with an `inception_model` and `real_features` (a FeatureStore or a
     (n,2048) device tensor of ground-truth features) the composites' features are kept as well (at most
     dist_options["max_images"] rows) and the record gains `kid` and / or `precision`, `recall` (dist_options: kid_subsets,
-    kid_subset_size, pr_k, seed); fid_capture then also receives "features". Without them the record is what it always was."""
+    kid_subset_size, pr_k, seed); fid_capture then also receives "features". Without them the record is what it always was.
+    `panel` (optional, (path, K[, gutter])): the first K rows of the FIRST batch - ground | input | output | composite - are written
+    to `path` as one greyscale PNG (lib.imageout.assemble_panel; K is clipped to the batch). It reuses the tensors of the pass: no
+    extra forward, no random draw, so the metrics and everything that follows are what they are without it."""
     lib = B.lib()
     meter = ReconMeter(device)
     fid_on = inception_model is not None and not _no_fid_stats(fid_stats)
@@ -84,6 +88,9 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         out = net(masked)                                                            # :134
         out = out.detach().contiguous()
         meter.update(inp, out, m)                                                    # :135-143
+        if panel is not None:
+            _write_panel(panel, inp, masked, out, m)
+            panel = None
         if fid_on or dist_on:
             comp = torch.empty_like(out)                                             # :136 out * m + masked
             B.check(lib.gi_mask_composite(B.get_ctx(out.device), B.ptr(masked), B.ptr(out), B.ptr(m), B.ptr(comp), out.numel()))
@@ -108,6 +115,16 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         if fid_capture is not None:
             fid_capture["features"] = store.features()
     return metric
+
+
+def _write_panel(panel, inp, masked, out, m):
+    """The sample panel of calculate_metric: K rows of ground | input | output | composite (masked + out * m)."""
+    from .. import imageout
+    path, k = panel[0], max(1, min(int(panel[1]), inp.shape[0]))
+    cols = [t[:k].contiguous() for t in (inp, masked, out, m)]
+    comp = torch.empty_like(cols[2])
+    B.check(B.lib().gi_mask_composite(B.get_ctx(comp.device), B.ptr(cols[1]), B.ptr(cols[2]), B.ptr(cols[3]), B.ptr(comp), comp.numel()))
+    imageout.write_png(path, imageout.assemble_panel(cols[:3] + [comp], gutter=int(panel[2]) if len(panel) > 2 else 2))
 
 
 def _no_fid_stats(fid_stats):

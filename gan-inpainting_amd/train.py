@@ -112,6 +112,8 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--dist-metrics needs --fid-weights: KID and precision / recall are computed from the Inception features")
             if a.kid_subsets < 1 or a.kid_subset_size < 2 or a.pr_k < 1 or a.dist_max_images < 2:
                 self.error("--kid-subsets >= 1, --kid-subset-size >= 2, --pr-k >= 1 and --dist-max-images >= 2")
+        if a.sample_rows < 0 or a.sample_gutter < 0:
+            self.error("--sample-rows and --sample-gutter must be >= 0")
         if a.resume not in ("", "auto") and len(a.experiments) > 1:
             self.error("--resume PATH names one experiment's state: give one -exp, or --resume auto")
         return a
@@ -198,6 +200,11 @@ def build_parser():
     parser.add_argument("--ema-decay", dest="ema_decay", type=float, default=0.0,
                         help="> 0: keep an exponential moving average of the generator's weights (one HIP pass per generator update); "
                              "the evaluation pass adds train_ema / test_ema and epoch<N>_G_ema.pt is saved next to epoch<N>_G.pt")
+    parser.add_argument("--sample-rows", dest="sample_rows", type=int, default=0, metavar="K",
+                        help="> 0: every evaluation also writes <outdir>/samples/{train,test}_epoch<N>.png (and ..._ema.png with --ema-decay): "
+                             "the first K rows of the pass's first batch as ground | input | output | composite (HIP panel kernel; no extra "
+                             "forward, no random draw: training is bit for bit what it is without the flag)")
+    parser.add_argument("--sample-gutter", dest="sample_gutter", type=int, default=2, help="white pixels between the panel's tiles")
     return parser
 
 

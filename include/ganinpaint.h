@@ -521,6 +521,32 @@ int gi_resize_to_tensor(gi_ctx* ctx, const void* tables_dev, const uint8_t* src,
 int gi_mask_generate(gi_ctx* ctx, int kind, uint64_t seed, const int64_t* keys_dev, int n, int H, int W, float* mask_out,
                      int* coverage_out);
 
+/* ---- image output (NOT in the reference): fp32 tensors back to 8-bit pictures, and a repaired window back into a
+ *      photograph of any size. All exact (integer arithmetic, or one fp32 multiply and rintf); tests/imageout_ref.py is the numpy
+ *      restatement, bit-exact with every entry. All asynchronous on the context's stream; invalid arguments return
+ *      GI_ERR_INVALID before anything is launched. Images are single-channel, row-major, dense. */
+/* dst[i] = (uint8) rintf(min(max(src[i], 0), 1) * 255.0f), NaN -> 0: round to nearest even, so every byte v round-trips through
+ * v / 255.0f (the truncating (x * 255).astype(uint8) of evaluate.py:156 stays with the FID path). Any count > 0, any dst
+ * alignment; src 4-byte aligned. */
+int gi_image_quantize(gi_ctx* ctx, const float* src, int64_t count, uint8_t* dst);
+/* cols_host: a HOST array of ncol (1 .. 8) device pointers, each a (n,1,H,W) fp32 batch. canvas: (n*(H+g)+g) x (ncol*(W+g)+g)
+ * uint8, g = gutter >= 0; tile (i, c) at row g + i*(H+g), column g + c*(W+g) holds the quantised cols[c][i], every other byte
+ * is 255; one launch writes every canvas byte exactly once. */
+int gi_panel_assemble(gi_ctx* ctx, const float* const* cols_host, int ncol, int n, int H, int W, int gutter, uint8_t* canvas);
+/* bbox_out[4 i ..] = (y0, x0, y1, x1), the inclusive bounding box of the bytes != 0 of mask i of (n,H,W) uint8; an empty mask
+ * gives (H, W, -1, -1). Integer min / max only: independent of any order. n <= 65535, H * W < 2^31 - 32. */
+int gi_mask_bbox(gi_ctx* ctx, const uint8_t* mask, int n, int H, int W, int* bbox_out);
+/* dst (wh, ww) = src[wy .. wy+wh)[wx .. wx+ww) of the (H, W) image; binarize != 0: every nonzero byte becomes 255. The window
+ * lies inside the image. */
+int gi_window_crop(gi_ctx* ctx, const uint8_t* src, int H, int W, int wy, int wx, int wh, int ww, int binarize, uint8_t* dst);
+/* Writes the window's bytes of dst (H, W) and no others (the caller has copied orig there): with A = (2r+1)^2, a(p) the number
+ * of hole pixels (mask != 0) in the (2r+1)^2 box around window pixel p (pixels outside the WINDOW count as 0) and
+ * alpha(p) = A on a hole pixel, else min(A, 2 a(p)):  dst(p) = (alpha * patch(p) + (A - alpha) * orig(p) + A / 2) / A  in
+ * integers. patch is dense (wh, ww); 0 <= r <= 63, r = 0 is a hard paste. At a straight hole edge the weight of the patch
+ * falls linearly from 1 to 0 at distance r + 1. */
+int gi_feather_paste(gi_ctx* ctx, const uint8_t* orig, const uint8_t* mask, int H, int W, int wy, int wx, int wh, int ww,
+                     const uint8_t* patch, int r, uint8_t* dst);
+
 /* ---- batch assembly from a device-resident image store (lib/data/cache.py): store is (n_store,h,w) uint8 on
  *      the device, rows_dev n int64 on the device, out (n,h,w) of out_kind: 0 fp32 (float)v / 255.0f (the ToTensor quotient of
  *      gi_resize_to_tensor), 1 int64 v (segmentation labels), 2 uint8 v. out[i][y][x] = f(store[rows[i]][y][flip_i ? w-1-x : x]).
