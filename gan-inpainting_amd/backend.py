@@ -104,6 +104,20 @@ PROTOTYPES = {
     "gi_vgg19_bind_grad": (_i, [_vp, _vp, _i64]),
     "gi_vgg19_perceptual_style_grad": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _f]),
     "gi_vgg19_grad_layer": (_i, [_vp, _i, _vp]),
+    "gi_lpips_create": (_i, [_vp, _i, _i, _i, _vp]),
+    "gi_lpips_destroy": (None, [_vp]),
+    "gi_lpips_param_floats": (_i64, [_vp]),
+    "gi_lpips_workspace_bytes": (_i64, [_vp]),
+    "gi_lpips_num_tensors": (_i, [_vp]),
+    "gi_lpips_tensor_desc": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "gi_lpips_bind": (_i, [_vp, _vp, _vp, _i64]),
+    "gi_lpips_sync_weights": (_i, [_vp]),
+    "gi_lpips_distance": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "gi_lpips_features": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gi_debug_lpips_conv1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gi_debug_lpips_fold": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "gi_debug_lpips_tap_ws_bytes": (_i64, [_i]),
+    "gi_debug_lpips_tap": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
     "gi_inception_create": (_i, [_vp, _i, _i, _vp]),
     "gi_inception_destroy": (None, [_vp]),
     "gi_inception_param_floats": (_i64, [_vp]),

@@ -32,6 +32,8 @@ def compat_args(state, world, nets):
         from .lib.models.augment import parse_policy
         out["diffaug"] = int(parse_policy(state["diffaug"]))
         out["diffaug_seed"] = int(state.get("diffaug_seed") or 0)
+    if state.get("lpips_model") is not None:      # --lpips-weights: the evaluation records of the resumed run carry `lpips` too
+        out["lpips"] = 1
     out["world_size"] = int(world)
     for name, net in nets.items():
         out[f"params/{name}"] = int(sum(p.numel() for p in net.parameters()))

@@ -10,7 +10,8 @@ Differences to the reference, all host-side and listed in DESIGN.md:
     one copy per batch (util.GradFlow), accumulated on the device;
   * the evaluation pass (minimaxgan_l1.py:234-240) runs lib.models.evaluate.calculate_metric on the
     train and test loaders (reconstruction metrics on fused HIP reductions; FID when state['inception_model']
-    and state['train_fid'] / state['test_fid'] are set (train.py --fid-weights), else -1); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch);
+    and state['train_fid'] / state['test_fid'] are set (train.py --fid-weights), else -1; `lpips` when state['lpips_model'] is set
+    (train.py --lpips-weights)); `state['eval_fn']`, if given, replaces it and is called with (net_G, loader, epoch);
   * opt-in (train.py --save-state / --resume / --ema-decay; none of it in the reference): the full training state in last_state.pt
     at epoch boundaries, resuming from it, and an averaged generator evaluated and saved next to the live one.
 """
@@ -155,6 +156,12 @@ def _panel_kwargs(state, mode, epoch, rank0, suffix=""):
         return {}
     outdir = state.get("outdir") or os.path.join(os.getcwd(), "runs")
     return {"panel": (os.path.join(outdir, "samples", f"{mode}_epoch{epoch:04d}{suffix}.png"), rows, int(state.get("sample_gutter", 2)))}
+
+
+def _lpips_kwargs(state):
+    """The opt-in `lpips_model` argument of evaluate.calculate_metric (train.py --lpips-weights); {} when off."""
+    model = state.get("lpips_model")
+    return {} if model is None else {"lpips_model": model}
 
 
 def _world():
@@ -342,7 +349,7 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                 rec_eval = {k: evaluate.calculate_metric(device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
                                                          inception_model=state.get("inception_model"), epoch=epoch,
                                                          prepare=eval_prepare(state, device, k, epoch), **_dist_kwargs(state, k),
-                                                         **_panel_kwargs(state, k, epoch, rank0))
+                                                         **_panel_kwargs(state, k, epoch, rank0), **_lpips_kwargs(state))
                             for k in ("train", "test") if loaders.get(k) is not None}
                 if ema is not None:                              # the same metrics of the averaged generator
                     with ema.applied():
@@ -351,7 +358,7 @@ def run_epochs(state, loaders, exp_dir, logger, device, net_G, nets_D, batch_fn,
                                 rec_eval[k + "_ema"] = evaluate.calculate_metric(
                                     device, loaders[k], net_G, fid_stats=_fid_stats(state, k), mode=k,
                                     inception_model=state.get("inception_model"), epoch=epoch, prepare=eval_prepare(state, device, k, epoch),
-                                    **_dist_kwargs(state, k), **_panel_kwargs(state, k, epoch, rank0, "_ema"))
+                                    **_dist_kwargs(state, k), **_panel_kwargs(state, k, epoch, rank0, "_ema"), **_lpips_kwargs(state))
                 eval_hist.append(rec_eval)
                 logger.info("VALIDATION: %s", ", ".join(f"{k} - {v}" for k, v in rec_eval.items()))
             if rank0:        # every rank holds the same replica: one writer

@@ -14,6 +14,7 @@ the composites as JPEG files and reads them back; here they keep the 8-bit trunc
 `(x * 255).astype(uint8)` but skip the file round trip (and with it JPEG's lossy coding).
 Beside FID, opt-in (`dist_metrics`, `real_features`): the Kernel Inception Distance and improved precision / recall of the same
 composites' features against stored ground-truth features (lib.fid.dist_metrics; the reference has neither).
+Also opt-in (`lpips_model`, lib.lpips.LPIPS): the learned perceptual distance between composite and ground truth (csrc/lpips.hip).
 Like the reference, calculate_metric does NOT switch the network to eval(): BatchNorm and Dropout run
 in whatever mode the caller left them (training mode in the plugins)."""
 import ctypes as C
@@ -52,7 +53,7 @@ class ReconMeter:
 @torch.no_grad()
 def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", inception_model=None, epoch=None,
                      is_flip_mask=False, prepare=None, fid_capture=None, real_features=None, dist_metrics=(), dist_options=None,
-                     panel=None):
+                     panel=None, lpips_model=None):
     """evaluate.py:85-177. `loader` yields (input, mask, _) like the reference's datasets; `prepare` (optional)
     maps a loader item to a (n,1,h,w) float32 device tensor (the device Resize + ToTensor for decoded bytes).
     `fid_capture` (optional dict, tests): receives the composites fed to Inception and the pass's (mu, sigma).
@@ -62,12 +63,16 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
     kid_subset_size, pr_k, seed); fid_capture then also receives "features". Without them the record is what it always was.
     `panel` (optional, (path, K[, gutter])): the first K rows of the FIRST batch - ground | input | output | composite - are written
     to `path` as one greyscale PNG (lib.imageout.assemble_panel; K is clipped to the batch). It reuses the tensors of the pass: no
-    extra forward, no random draw, so the metrics and everything that follows are what they are without it."""
+    extra forward, no random draw, so the metrics and everything that follows are what they are without it.
+    `lpips_model` (optional, lib.lpips.LPIPS): every batch's composite (out * m + masked, NOT truncated to 8 bits) is compared with its
+    ground truth; the per-image distances are summed on the device and read back once, and the record gains `lpips`, their mean.
+    Without it the record and every launch are what they are without the argument."""
     lib = B.lib()
     meter = ReconMeter(device)
     fid_on = inception_model is not None and not _no_fid_stats(fid_stats)
     dist_on = bool(dist_metrics) and inception_model is not None and real_features is not None
     stats = store = None
+    lpips_sum, lpips_count = None, 0
     if fid_on or dist_on:
         from ..fid import fid_score
     if fid_on:
@@ -91,10 +96,15 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         if panel is not None:
             _write_panel(panel, inp, masked, out, m)
             panel = None
-        if fid_on or dist_on:
+        if lpips_model is not None or fid_on or dist_on:
             comp = torch.empty_like(out)                                             # :136 out * m + masked
             B.check(lib.gi_mask_composite(B.get_ctx(out.device), B.ptr(masked), B.ptr(out), B.ptr(m), B.ptr(comp), out.numel()))
-            comp = fid_score.quantize8(comp)                                         # :155-158 without the file
+        if lpips_model is not None:                                                  # the composite as it is, not truncated to 8 bits
+            d = lpips_model.distance(comp, inp).sum()
+            lpips_sum = d if lpips_sum is None else lpips_sum + d
+            lpips_count += inp.shape[0]
+        if fid_on or dist_on:
+            comp = fid_score.quantize8(comp)                                         # :155-158 without the file (a new tensor)
             feats = inception_model.features(comp)
             if fid_on:
                 stats.update(feats)
@@ -114,6 +124,8 @@ def calculate_metric(device, loader, net, fid_stats=(-1, -1), mode="test", incep
         metric.update(dm.evaluate(real_features, store, dist_metrics, dist_options))
         if fid_capture is not None:
             fid_capture["features"] = store.features()
+    if lpips_model is not None:
+        metric["lpips"] = float(lpips_sum) / lpips_count if lpips_count else float("nan")
     return metric
 
 

@@ -160,6 +160,11 @@ def build_parser():
     parser.add_argument("--pr-k", dest="pr_k", type=int, default=3, help="precision / recall: the k of the k-NN radii")
     parser.add_argument("--dist-max-images", dest="dist_max_images", type=int, default=10000,
                         help="--dist-metrics keeps at most this many feature rows per set (the first ones; precision / recall is O(n^2 d))")
+    parser.add_argument("--lpips-weights", dest="lpips_weights", nargs="+", default=None, metavar="FILE",
+                        help="local state dict(s) of the LPIPS metric, merged by key: a torchvision vgg16 state dict plus the lpips "
+                             "package's vgg.pth, or one full LPIPS state dict. The evaluation pass then adds `lpips`, the mean learned "
+                             "perceptual distance between composite and ground truth (HIP, lib/lpips.py); every rank evaluates its "
+                             "shard. Nothing is ever downloaded; without the flag nothing changes")
     parser.add_argument("--data", default="synthetic")
     parser.add_argument("--masks", choices=["files", "rect", "freeform"], default="files",
                         help="files: the masks the data supplies (the mask_source files of --data <dir>; host rectangles for "
@@ -257,7 +262,8 @@ def main(argv=None):
         segmentation_model = networks.UnetGenerator(1, 4, 7, ngf=32, norm_layer=functools.partial(torch.nn.BatchNorm2d, affine=True,
                                                     track_running_stats=True), use_dropout='False', dtype=args.dtype).eval()   # train.py:171-175
     state.update({"masks": args.masks, "mask_seed": args.mask_seed})
-    state.update({"train_fid": None, "test_fid": None, "inception_model": None, "segmentation_model": segmentation_model})
+    state.update({"train_fid": None, "test_fid": None, "inception_model": None, "lpips_model": None,
+                  "segmentation_model": segmentation_model})
     if args.fid_weights:
         # train.py:154-180: ground-truth statistics of the train and test loaders, once. Every rank computes them on its own shard
         # (no broadcast: each rank also evaluates its own shard); the ground truths pass the same 8-bit truncation as the composites
@@ -282,6 +288,14 @@ def main(argv=None):
             if store is not None:
                 state[k + "_feats"] = store
         state["inception_model"] = inception_model
+    if args.lpips_weights:
+        from gan_inpainting_amd.lib.lpips import LPIPS
+        merged = {}
+        for path in args.lpips_weights:
+            merged.update(torch.load(path, map_location="cpu"))
+        lpips_model = LPIPS()
+        lpips_model.load_state_dict(merged)
+        state["lpips_model"] = lpips_model.to(torch.device("cuda", torch.cuda.current_device()))
     for name in args.experiments:
         exp = importlib.import_module(f"gan_inpainting_amd.experiment_list.{name}")
         exp.begin(state, loaders)

@@ -419,6 +419,31 @@ int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* 
                                    float weight_s, float* out2, float* per_tap10, float* grad_out, float gscale);
 int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw_f32);
 
+/* LPIPS (Zhang et al. 2018; `lpips` v0.1 with net = 'vgg', normalize = True, spatial = False) between grey images repeated
+ * over 3 channels: VGG-16 taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3, each before its max pool. Forward only (a metric).
+ * H, W: multiples of 16, >= 16; 2 * max_pairs * H * W * 64 < 2^31. params (fp32, gi_lpips_tensor_desc gives name, shape, offset):
+ * the 13 convolutions "features.<i>.weight|bias" (torchvision vgg16 indices 0,2,5,7,10,12,14,17,19,21,24,26,28), the five
+ * "lin<k>.model.1.weight" vectors (64,128,256,512,512), "scaling_layer.shift" and "scaling_layer.scale" (3 each). The scaling
+ * layer is folded into the first convolution at gi_lpips_sync_weights, exactly: the zero padding applies to the scaled input.
+ * gi_lpips_distance: a, b (n,1,H,W) fp32 in [0,1], n <= max_pairs; out_n[i] = sum_l d_l[i],
+ * d_l[i] = mean over pixels of sum_c lin_lc (fa / (|fa|_2 + 1e-10) - fb / (|fb|_2 + 1e-10))^2, norms over the channels of a pixel;
+ * per_layer_5n (may be NULL): d_l[i] at [l * n + i]. fp16 MFMA convolutions, fp32 per pixel, fp64 spatial sums in a fixed order:
+ * bit-reproducible, identical inputs give exactly 0, and the first layer and the tap kernels give an image the same bits wherever it
+ * sits in the batch and whatever n is. Bit-equality ACROSS different n is not guaranteed through the twelve 3x3 convolutions: which
+ * implicit-GEMM kernel serves a layer depends on its grid, which grows with n (calls with the same n always agree).
+ * gi_lpips_features: the map of tap 0..4 as (n,C,h,w) fp32 (parity checks). */
+typedef struct gi_lpips gi_lpips;
+int gi_lpips_create(gi_ctx* ctx, int H, int W, int max_pairs, gi_lpips** out);
+void gi_lpips_destroy(gi_lpips* v);
+int64_t gi_lpips_param_floats(const gi_lpips* v);
+int64_t gi_lpips_workspace_bytes(const gi_lpips* v);
+int gi_lpips_num_tensors(const gi_lpips* v);
+int gi_lpips_tensor_desc(const gi_lpips* v, int index, char* name, int name_cap, int* shape4, int64_t* offset);
+int gi_lpips_bind(gi_lpips* v, const float* params, void* ws, int64_t ws_bytes);   /* ws 256-byte, params 16-byte aligned */
+int gi_lpips_sync_weights(gi_lpips* v);                                            /* after params change */
+int gi_lpips_distance(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n);
+int gi_lpips_features(gi_lpips* v, const float* x, int n, int tap, float* out_nchw);
+
 /* ---- Frechet Inception Distance (reference lib/fid/): Inception-V3 pool3 features + streaming statistics ----
  * The FID variant of Inception-V3 (lib/fid/inception.py: average pools that do not count padding in Mixed_5b..5d,
  * 6b..6e, 7b; a max pool in Mixed_7c), forward only, up to the 2048-wide global average (output block 3).
@@ -829,6 +854,20 @@ int gi_debug_vgg_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, 
 /* dimg (n,H,W fp32) = gscale * sc[1] * adjoint of the 1 -> 64 convolution w1 [64][9] applied to D (n,H,W,64) fp16 */
 int gi_debug_vgg_conv1_adjoint(gi_ctx* ctx, const void* D, const float* w1, const float* sc, float gscale, float* dimg, int n,
                                int H, int W);
+/* ---- the LPIPS kernels on their own (test seam; csrc/lpips.hip, restated by tests/lpips_ref.py). Each entry checks what its kernel
+ * assumes and runs the host launch code the handle uses.
+ * conv1: out [2n][H][W][64] fp16 = relu(bias + sum_tap wA[.][tap] x[tap] + sum_tap wB[.][tap] [tap inside the image]) for the images
+ * xa, xb (n,H,W fp32 each); wA, wB [64][9], bias [64] fp32; W a multiple of 16.
+ * fold: w [64][3][3][3], shift[3], scale[3] -> wA = sum_c w * 2 / scale_c, wB = sum_c w * (-1 - shift_c) / scale_c.
+ * tap: F [2n][H][W][C] fp16 (image i pairs with image i + n; C = 64, 128, 256 or 512), lin [C] fp32 -> d_n[i]; with pooled (H, W even):
+ * the fused form, which also writes the 2x2 max pool [2n][H/2][W/2][C]. F, lin, pooled 16-byte aligned; ws: gi_debug_lpips_tap_ws_bytes(n)
+ * bytes, 8-byte aligned. */
+int gi_debug_lpips_conv1(gi_ctx* ctx, const float* xa, const float* xb, int n, int H, int W, const float* wA, const float* wB,
+                         const float* bias, void* out);
+int gi_debug_lpips_fold(gi_ctx* ctx, const float* w, const float* shift, const float* scale, float* wA, float* wB);
+int64_t gi_debug_lpips_tap_ws_bytes(int n);
+int gi_debug_lpips_tap(gi_ctx* ctx, const void* F, int n, int H, int W, int C, const float* lin, void* ws, int64_t ws_bytes,
+                       float* d_n, void* pooled);
 /* fp32 master [a][16][b] -> T [a][16*b] (w_packed) and T [4][b][4*a] (w_phase); either may be NULL */
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase);
 int gi_convert(gi_ctx* ctx, int dtype, const float* src, void* dst, int64_t count);      /* fp32 -> T */
