@@ -202,6 +202,9 @@ PROTOTYPES = {
     "gi_debug_sn_power_iteration": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "gi_debug_sn_project_add": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "gi_debug_stat_acc_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
+    "gi_debug_head_forward": (_i, [_vp, _i, _vp]),
+    "gi_debug_head_backward": (_i, [_vp, _i, _vp]),
+    "gi_debug_head_scratch_bytes": (_i64, [_i, _i, _i]),
     "gi_debug_vgg_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "gi_debug_vgg_conv1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gi_debug_vgg_maxpool2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
@@ -260,6 +263,30 @@ class ActBnBwdArgs(C.Structure):
                 ("groups", _i), ("stat_stride", _i),
                 ("acc", _vp), ("acc_reps", _i), ("zero_next", _vp), ("zero_words", _i),
                 ("reduce_done", _i)]
+
+
+class HeadArgs(C.Structure):
+    """gi_head_args (include/ganinpaint.h): gi_debug_head_forward."""
+    _fields_ = [("a4", _vp), ("w5", _vp), ("wl", _vp), ("bl", _vp), ("h", _vp), ("out", _vp),
+                ("n", _i), ("Hh", _i), ("Wh", _i), ("c", _i), ("sigmoid", _i),
+                ("out2", _vp),
+                ("scale4", _vp), ("shift4", _vp), ("n_per_group", _i), ("gstride", _i),
+                ("tbuf", _vp), ("tbuf_bytes", _i64),
+                ("bn", C.POINTER(BnAccArgs))]
+
+
+class HeadBwdArgs(C.Structure):
+    """gi_head_bwd_args (include/ganinpaint.h): gi_debug_head_backward; bwd_applied is returned."""
+    _fields_ = [("a4", _vp), ("w5", _vp), ("wl", _vp), ("h", _vp), ("out", _vp), ("dy", _vp), ("da4", _vp),
+                ("dw5", _vp), ("dwl", _vp), ("dbl", _vp), ("dh", _vp),
+                ("n", _i), ("Hh", _i), ("Wh", _i), ("c", _i), ("sigmoid", _i), ("loss_scale", _f),
+                ("scratch", _vp), ("scratch_bytes", _i64),
+                ("scale4", _vp), ("shift4", _vp), ("n_per_group", _i), ("gstride", _i),
+                ("bwd_x", _vp),
+                ("bwd_scale", _vp), ("bwd_shift", _vp), ("bwd_mean", _vp), ("bwd_inv", _vp),
+                ("bwd_stride", _i), ("bwd_n_per_group", _i), ("bwd_reps", _i), ("bwd_slope", _f),
+                ("bwd_acc", _vp),
+                ("bwd_applied", _i)]
 
 
 class BackendError(RuntimeError):

@@ -522,6 +522,75 @@ int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps,
   return GI_OK;
 }
 
+// ---- the critic head (head.hip) on its own: what tests/test_head_gpu.py drives ---------------------------------------------------
+namespace {
+// the shape checks shared by the head's forward and backward; *pops = the number of BatchNorm populations the images fall into
+int dbg_head_shape(const char* who, int dtype, int n, int Hh, int Wh, int c, int n_per_group, int* pops) {
+  GI_REQUIRE(dbg_dtype_ok(dtype), "%s: dtype=%d", who, dtype);
+  GI_REQUIRE(n >= 1 && c >= 1 && c % dbg_epc(dtype) == 0, "%s: n=%d c=%d (c a multiple of %d)", who, n, c, dbg_epc(dtype));
+  GI_REQUIRE(Hh >= 4 && Wh >= 4, "%s: feature map %dx%d below the 4x4 kernel", who, Hh, Wh);
+  GI_REQUIRE(n_per_group >= 0 && (n_per_group == 0 || n % n_per_group == 0), "%s: n_per_group=%d does not divide n=%d", who, n_per_group, n);
+  *pops = n_per_group > 0 ? n / n_per_group : 1;
+  return GI_OK;
+}
+}  // namespace
+
+int gi_debug_head_forward(gi_ctx* ctx, int dtype, const gi_head_args* s) {
+  GI_REQUIRE(ctx && s && s->a4 && s->w5 && s->wl && s->bl && s->h && s->out, "debug_head_forward: null pointer");
+  int pops = 1;
+  GI_TRY(dbg_head_shape("debug_head_forward", dtype, s->n, s->Hh, s->Wh, s->c, s->n_per_group, &pops));
+  GI_REQUIRE((s->scale4 == nullptr) == (s->shift4 == nullptr), "debug_head_forward: scale4 and shift4 go together");
+  GI_REQUIRE(!s->scale4 || pops == 1 || (pops == 2 && s->gstride >= s->c), "debug_head_forward: %d populations, gstride=%d for %d channels", pops,
+             s->gstride, s->c);
+  GI_REQUIRE(s->tbuf_bytes >= 0 && (s->tbuf_bytes == 0 || s->tbuf), "debug_head_forward: tbuf_bytes=%lld without tbuf", (long long)s->tbuf_bytes);
+  HeadArgs a;
+  a.a4 = s->a4; a.w5 = s->w5; a.wl = s->wl; a.bl = s->bl; a.h = s->h; a.out = s->out;
+  a.n = s->n; a.Hh = s->Hh; a.Wh = s->Wh; a.c = s->c; a.sigmoid = s->sigmoid; a.out2 = s->out2;
+  a.scale4 = s->scale4; a.shift4 = s->shift4; a.n_per_group = s->n_per_group; a.gstride = s->gstride;
+  a.tbuf = s->tbuf_bytes > 0 ? s->tbuf : nullptr; a.tbuf_bytes = s->tbuf_bytes;
+  BnAccArgs bn;
+  if (s->bn) {
+    GI_TRY(dbg_bn_acc("debug_head_forward", s->c, s->bn, bn));
+    GI_REQUIRE(bn.groups == pops, "debug_head_forward: %d accumulator populations for %d populations of images", bn.groups, pops);
+    a.bn = &bn;
+  }
+  return op_head_forward(ctx->stream, dtype, a);
+}
+
+int gi_debug_head_backward(gi_ctx* ctx, int dtype, gi_head_bwd_args* s) {
+  GI_REQUIRE(ctx && s && s->w5 && s->wl && s->h && s->out && s->dy && s->da4, "debug_head_backward: null pointer");
+  GI_REQUIRE(s->dh, "debug_head_backward: dh is missing (the generic kernels write it)");
+  s->bwd_applied = 0;
+  int pops = 1, bpops = 1;
+  GI_TRY(dbg_head_shape("debug_head_backward", dtype, s->n, s->Hh, s->Wh, s->c, s->n_per_group, &pops));
+  GI_REQUIRE(!s->dw5 || (s->dwl && s->a4), "debug_head_backward: dw5 without dwl / a4");
+  GI_REQUIRE((s->scale4 == nullptr) == (s->shift4 == nullptr), "debug_head_backward: scale4 and shift4 go together");
+  GI_REQUIRE(!s->scale4 || pops == 1 || (pops == 2 && s->gstride >= s->c), "debug_head_backward: %d populations, gstride=%d for %d channels", pops,
+             s->gstride, s->c);
+  GI_REQUIRE(s->scratch_bytes >= 0 && (s->scratch_bytes == 0 || s->scratch), "debug_head_backward: scratch_bytes=%lld without scratch",
+             (long long)s->scratch_bytes);
+  if (s->bwd_acc) {
+    GI_REQUIRE(s->bwd_x && s->bwd_scale && s->bwd_shift && s->bwd_mean && s->bwd_inv, "debug_head_backward: bwd_acc without x / scale / shift / mean / inv");
+    GI_REQUIRE(s->bwd_reps >= 1 && s->bwd_reps <= GI_STAT_MAXREP && gi_is_pow2(s->bwd_reps), "debug_head_backward: bwd_reps=%d (1, 2 or %d)", s->bwd_reps,
+               GI_STAT_MAXREP);
+    GI_TRY(dbg_head_shape("debug_head_backward", dtype, s->n, s->Hh, s->Wh, s->c, s->bwd_n_per_group, &bpops));
+    GI_REQUIRE(bpops == 1 || (bpops == 2 && s->bwd_stride >= s->c), "debug_head_backward: %d populations, bwd_stride=%d for %d channels", bpops,
+               s->bwd_stride, s->c);
+  }
+  HeadBwdArgs a;
+  a.a4 = s->a4; a.w5 = s->w5; a.wl = s->wl; a.h = s->h; a.out = s->out; a.dy = s->dy; a.da4 = s->da4;
+  a.dw5 = s->dw5; a.dwl = s->dwl; a.dbl = s->dbl; a.dh = s->dh;
+  a.n = s->n; a.Hh = s->Hh; a.Wh = s->Wh; a.c = s->c; a.sigmoid = s->sigmoid; a.loss_scale = s->loss_scale;
+  a.scratch = s->scratch_bytes > 0 ? s->scratch : nullptr; a.scratch_bytes = s->scratch_bytes;
+  a.scale4 = s->scale4; a.shift4 = s->shift4; a.n_per_group = s->n_per_group; a.gstride = s->gstride;
+  a.bwd_x = s->bwd_x; a.bwd_scale = s->bwd_scale; a.bwd_shift = s->bwd_shift; a.bwd_mean = s->bwd_mean; a.bwd_inv = s->bwd_inv;
+  a.bwd_stride = s->bwd_stride; a.bwd_n_per_group = s->bwd_n_per_group; a.bwd_reps = s->bwd_reps; a.bwd_slope = s->bwd_slope;
+  a.bwd_acc = s->bwd_acc; a.bwd_applied = &s->bwd_applied;
+  return op_head_backward(ctx->stream, dtype, a);
+}
+
+int64_t gi_debug_head_scratch_bytes(int max_n, int Hh, int Wh) { return op_head_scratch_bytes(max_n, Hh, Wh); }
+
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase) {
   GI_REQUIRE(ctx && w, "pack_weights: null pointer");
   return op_pack_weights(ctx->stream, dtype, w, ca, cb, w_packed, w_phase);

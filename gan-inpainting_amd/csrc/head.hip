@@ -590,6 +590,7 @@ int op_head_forward(hipStream_t st, int dtype, const HeadArgs& a) {
     while (a.n * slices < 256 && npx / (slices * 2) >= 256) slices *= 2;
     if (slices > 1 && a.tbuf && a.tbuf_bytes >= (int64_t)a.n * npx * 16 * 4) {
       const int lds2 = (16) * 4 + 16 * 512 * 2 + 2 * 512 * 4;
+      gi_note_kernel("head_fwd512_sliced");
       hipLaunchKernelGGL(head_fwd512_kernel, dim3(a.n * slices), dim3(1024), lds2, st, (const char*)a.a4, a.w5, a.wl, a.bl, a.h, a.out, a.out2, a.Hh,
                          a.Wh, a.sigmoid, a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, a.tbuf, slices, fa, use_fa);
       GI_LAUNCH_CHECK();
@@ -597,11 +598,13 @@ int op_head_forward(hipStream_t st, int dtype, const HeadArgs& a) {
       GI_LAUNCH_CHECK();
       return GI_OK;
     }
+    gi_note_kernel("head_fwd512");
     hipLaunchKernelGGL(head_fwd512_kernel, dim3(a.n), dim3(1024), lds, st, (const char*)a.a4, a.w5, a.wl, a.bl, a.h, a.out, a.out2, a.Hh, a.Wh, a.sigmoid,
                        a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, (float*)nullptr, 1, fa, use_fa);
     GI_LAUNCH_CHECK();
     return GI_OK;
   }
+  gi_note_kernel("head_fwd");
   if (dtype == GI_F16)
     hipLaunchKernelGGL(head_conv_kernel<half_t>, dim3(blocks), dim3(256), 0, st, (const char*)a.a4, a.w5, a.h, a.Hh, a.Wh, a.c);
   else
@@ -626,6 +629,7 @@ int op_head_backward(hipStream_t st, int dtype, const HeadBwdArgs& a) {
     hf.slope = a.bwd_slope; hf.acc = (a.bwd_acc && a.bwd_x) ? a.bwd_acc : nullptr;
     if (!wg || (a.scratch && a.scratch_bytes >= (int64_t)nb * 8192 * 4)) {
       GI_REQUIRE(!wg || a.dwl, "head: dw5 without dwl");
+      gi_note_kernel("head_bwd512");
       hipLaunchKernelGGL(head_bwd512_kernel, dim3(wg ? 2 * nb : nb), dim3(256), 0, st, a.dy, a.out, a.h, a.wl, a.w5, (const char*)a.a4,
                          (char*)a.da4, a.scratch, a.dwl, a.dbl, a.n, a.Hh, a.Wh, bands, a.sigmoid, a.loss_scale,
                          a.scale4, a.shift4, a.n_per_group > 0 ? a.n_per_group : a.n, a.gstride, hf);
@@ -638,6 +642,7 @@ int op_head_backward(hipStream_t st, int dtype, const HeadBwdArgs& a) {
       return GI_OK;
     }
   }
+  gi_note_kernel("head_bwd");
   hipLaunchKernelGGL(head_linear_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, st, a.dy, a.out, a.h, a.wl, a.dh, a.dwl,
                      a.dbl, a.n, P, a.sigmoid);
   GI_LAUNCH_CHECK();

@@ -818,6 +818,55 @@ int gi_debug_sn_project_add(gi_ctx* ctx, const float* g, const float* w_eff, con
  * one workgroup per row and one lane per channel as the producing kernels do */
 int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends,
                           int rows);
+/* ---- the PatchGAN critic head on its own (test seam) ------------------------------------------------------------------------
+ * Conv2d(c,1,4,1,0) + Flatten + Linear(P,1) [+ Sigmoid] of csrc/head.hip, forward and backward; each entry checks what the kernels
+ * assume (GI_ERR_INVALID before any launch) and forwards to the dispatcher the networks call; nothing here is on a training path.
+ * a4 is dense NHWC (n,Hh,Wh,c) of the compute type, c a multiple of the 16-byte chunk, Hh, Wh >= 4; Ph = Hh - 3, Pw = Wh - 3,
+ * P = Ph * Pw; w5 fp32 [16][c] (tap = ky*4 + kx), wl fp32 [P], bl fp32 [1]. tests/head_ref.py restates every formula in fp64.
+ * forward:  h[i,py,px] = sum_{ky,kx,ch} x[i,py+ky,px+kx,ch] * w5[ky*4+kx][ch];  out[i] = [sigmoid](bl + sum_p wl[p] * h[i,p]); out2
+ *           (or NULL) a second copy. x = a4, or with scale4 / shift4 (fp16, c = 512 only) x = fp16(lrelu(fma(a4, scale4[g], shift4[g])))
+ *           with slope 0.2, g = i / n_per_group (0: one population), population g's vectors at + g * gstride floats. bn (with scale4):
+ *           the vectors are derived from the exact accumulators and published at bn->scale / shift / save_mean / save_invstd, the
+ *           running statistics moved population by population and bn->zero_next cleared (bn->out_stride == gstride). tbuf (or NULL):
+ *           n * Hh * Wh * 16 floats that let the fp16 c = 512 kernel slice a large map over workgroups.
+ * backward: dz[i] = dy[i] * (sigmoid ? out[i] * (1 - out[i]) : 1); dh[i,p] = dz[i] * wl[p];
+ *           da4[i,y,x,ch] = T(loss_scale * sum_tap dh[i,y-ky,x-kx] * w5[tap][ch]) over the valid positions;
+ *           dw5[tap][ch] += sum_{i,p} dh[i,p] * x[i,p+tap,ch]; dwl[p] += sum_i dz[i] * h[i,p]; dbl += sum_i dz[i]   (NULL: frozen).
+ *           dh: (n,P) scratch, written by the generic kernels only. scratch (or NULL): the weight-gradient partials,
+ *           gi_debug_head_scratch_bytes(); the fp16 c = 512 kernels fall back to the generic ones when it is too small, the generic
+ *           ones to float atomics. bwd_acc with bwd_x (fp16 c = 512): with x = bwd_x (dense raw tensor) and the stored da4,
+ *           dz = da4 * (fma(x, bwd_scale, bwd_shift) > 0 ? 1 : bwd_slope), xhat = (x - bwd_mean) * bwd_inv: sum dz (quantity 0) and
+ *           sum dz * xhat (quantity 1) per channel are added to the accumulator block, population i / bwd_n_per_group, vectors
+ *           bwd_stride floats apart, bwd_reps (1, 2 or 4) replicas; bwd_applied = 1 when the kernel did it.
+ * gi_debug_last_kernel() names the path: "head_fwd512", "head_fwd512_sliced", "head_fwd", "head_bwd512", "head_bwd". */
+typedef struct gi_head_args {
+  const void* a4; const float* w5; const float* wl; const float* bl;
+  float* h; float* out;
+  int n, Hh, Wh, c, sigmoid;
+  float* out2;
+  const float* scale4; const float* shift4; int n_per_group, gstride;
+  float* tbuf; int64_t tbuf_bytes;
+  const gi_bn_acc_args* bn;
+} gi_head_args;
+typedef struct gi_head_bwd_args {
+  const void* a4; const float* w5; const float* wl; const float* h; const float* out;
+  const float* dy;
+  void* da4;
+  float* dw5; float* dwl; float* dbl;
+  float* dh;
+  int n, Hh, Wh, c, sigmoid;
+  float loss_scale;
+  float* scratch; int64_t scratch_bytes;
+  const float* scale4; const float* shift4; int n_per_group, gstride;
+  const void* bwd_x;
+  const float* bwd_scale; const float* bwd_shift; const float* bwd_mean; const float* bwd_inv;
+  int bwd_stride, bwd_n_per_group, bwd_reps; float bwd_slope;
+  unsigned long long* bwd_acc;
+  int bwd_applied;                               /* returned */
+} gi_head_bwd_args;
+int gi_debug_head_forward(gi_ctx* ctx, int dtype, const gi_head_args* a);
+int gi_debug_head_backward(gi_ctx* ctx, int dtype, gi_head_bwd_args* a);
+int64_t gi_debug_head_scratch_bytes(int max_n, int Hh, int Wh);
 /* ---- the VGG-19 loss path's kernels on their own (test seam) ------------------------------------------------------------------
  * Each entry checks what its kernel assumes (GI_ERR_INVALID before any launch) and runs the host launch code of csrc/vgg.hip that the
  * network runners use; nothing here is on a training path. Feature maps are dense NHWC fp16; tests/vgg_ops_ref.py restates every op.
