@@ -202,6 +202,7 @@ PROTOTYPES = {
     "gi_debug_sn_power_iteration": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "gi_debug_sn_project_add": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "gi_debug_stat_acc_add": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
+    "gi_debug_pack_weights_batch": (_i, [_vp, _i, _vp, _i]),
     "gi_debug_head_forward": (_i, [_vp, _i, _vp]),
     "gi_debug_head_backward": (_i, [_vp, _i, _vp]),
     "gi_debug_head_scratch_bytes": (_i64, [_i, _i, _i]),
@@ -263,6 +264,13 @@ class ActBnBwdArgs(C.Structure):
                 ("groups", _i), ("stat_stride", _i),
                 ("acc", _vp), ("acc_reps", _i), ("zero_next", _vp), ("zero_words", _i),
                 ("reduce_done", _i)]
+
+
+class PackJob(C.Structure):
+    """gi_pack_job (include/ganinpaint.h): one layer of gi_debug_pack_weights_batch."""
+    _fields_ = [("w", _vp), ("packed", _vp), ("phase", _vp),
+                ("ca", _i), ("cb", _i), ("scale_on_b", _i),
+                ("scale", _vp)]
 
 
 class HeadArgs(C.Structure):

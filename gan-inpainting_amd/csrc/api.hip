@@ -522,6 +522,30 @@ int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps,
   return GI_OK;
 }
 
+// the one-launch weight re-pack of a network's update (pack_batch_kernel / pack_batch64_kernel) on jobs the caller describes
+int gi_debug_pack_weights_batch(gi_ctx* ctx, int dtype, const gi_pack_job* jobs, int n) {
+  GI_REQUIRE(ctx && jobs, "debug_pack_weights_batch: null pointer");
+  GI_REQUIRE(dbg_dtype_ok(dtype), "debug_pack_weights_batch: dtype=%d", dtype);
+  GI_REQUIRE(n >= 1 && n <= 16, "debug_pack_weights_batch: %d jobs (1 .. 16)", n);
+  PackJobs P;
+  P.n = 0;
+  bool all64 = true;
+  for (int i = 0; i < n; ++i) all64 = all64 && jobs[i].ca > 0 && jobs[i].cb > 0 && jobs[i].ca % 64 == 0 && jobs[i].cb % 64 == 0;
+  for (int i = 0; i < n; ++i) {
+    const gi_pack_job& s = jobs[i];
+    GI_REQUIRE(s.w, "debug_pack_weights_batch: job %d has no weights", i);
+    GI_REQUIRE(s.ca >= 1 && s.cb >= 1 && s.ca <= 4096 && s.cb <= 4096, "debug_pack_weights_batch: job %d ca=%d cb=%d", i, s.ca, s.cb);
+    GI_REQUIRE(s.scale_on_b == 0 || s.scale_on_b == 1, "debug_pack_weights_batch: job %d scale_on_b=%d", i, s.scale_on_b);
+    // the 64 x 64 kernel moves four values per lane: 16-byte chunks of fp32, 8-byte ones of fp16
+    const uintptr_t in = reinterpret_cast<uintptr_t>(s.w) | (s.scale_on_b ? reinterpret_cast<uintptr_t>(s.scale) : 0);
+    const uintptr_t out = reinterpret_cast<uintptr_t>(s.packed) | reinterpret_cast<uintptr_t>(s.phase);
+    GI_REQUIRE(!all64 || ((in & 15) == 0 && (out & (dtype == GI_F16 ? 7 : 15)) == 0), "debug_pack_weights_batch: job %d is not aligned for the 64-tile kernel", i);
+    PackJob& J = P.j[P.n++];
+    J.w = s.w; J.packed = s.packed; J.phase = s.phase; J.ca = s.ca; J.cb = s.cb; J.tile0 = 0; J.scale_on_b = s.scale_on_b; J.scale = s.scale;
+  }
+  return op_pack_weights_batch(ctx->stream, dtype, P);
+}
+
 // ---- the critic head (head.hip) on its own: what tests/test_head_gpu.py drives ---------------------------------------------------
 namespace {
 // the shape checks shared by the head's forward and backward; *pops = the number of BatchNorm populations the images fall into

@@ -102,8 +102,11 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const float* ground, co
 }
 __global__ void __launch_bounds__(256) mask_composite_kernel(const float* masked, const float* gen, const float* mask_c,
                                                              float* out, int64_t count) {
+  // two roundings like the reference (mul, then add): without the pragma the pair contracts to one fused multiply-add, which differs
+  // by an ulp on a third of the elements once mask_c is fractional (__fmul_rn / __fadd_rn are plain operators here and contract too)
+#pragma clang fp contract(off)
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256)
-    out[i] = masked[i] + gen[i] * mask_c[i];   // two roundings like the reference (mul, then add)
+    out[i] = masked[i] + gen[i] * mask_c[i];
 }
 __global__ void __launch_bounds__(256) mul_kernel(const float* a, const float* b, float* out, int64_t count) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) out[i] = a[i] * b[i];
@@ -125,6 +128,14 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// The masked difference x m - y m with its three roundings, as the reference's y * mask - yhat * mask has them: with one product fused
+// into the difference, x == y under a fractional mask would leave the rounding residue of x m instead of 0 (an L1 gradient of
+// +-m / count there, and no sqrt(eps) for equal inputs). The compiler happens to keep them apart today; the pragma makes it the rule.
+__device__ __forceinline__ float masked_diff(float x, float y, float m) {
+#pragma clang fp contract(off)
+  return x * m - y * m;
+}
+
 // kind: 0 sum|a-b| ; 1 sum (a-b)^2 ; 2/3 masked versions (y*m - yhat*m), second sum = count(m != 0)
 __global__ void __launch_bounds__(256) loss_partial_kernel(const float* a, const float* b, const float* m, int64_t count,
                                                            int kind, float* scratch) {
@@ -134,7 +145,7 @@ __global__ void __launch_bounds__(256) loss_partial_kernel(const float* a, const
     float d;
     if (m) {
       const float mm = m[i];
-      d = b[i] * mm - a[i] * mm;
+      d = masked_diff(b[i], a[i], mm);
       cnt += (mm != 0.f) ? 1.0 : 0.0;
     } else {
       d = a[i] - b[i];
@@ -167,7 +178,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* a, const fl
   const float l = loss[0], den = loss[1];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
     float d, mm = 1.f;
-    if (m) { mm = m[i]; d = a[i] * mm - b[i] * mm; }
+    if (m) { mm = m[i]; d = masked_diff(a[i], b[i], mm); }
     else d = a[i] - b[i];
     float g;
     if (gkind == 0) g = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) / den;
@@ -188,7 +199,8 @@ __global__ void __launch_bounds__(256) adv_loss_kernel(const float* pred, int n,
     const float p = pred[i];
     float l, g;
     if (kind == 0) {  // nn.BCELoss: log clamped at -100; backward (p-t)/max(p(1-p),1e-12)
-      const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(logf(1.f - p), -100.f);
+      // log1p: 1.f - p is 1 for p < 2^-25, and the loss of a confidently rejected sample would read 0 instead of p
+      const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(log1pf(-p), -100.f);
       l = -(target * lp + (1.f - target) * l1p);
       g = (p - target) / fmaxf(p * (1.f - p), 1e-12f);
     } else if (kind == 1) {

@@ -818,6 +818,17 @@ int gi_debug_sn_project_add(gi_ctx* ctx, const float* g, const float* w_eff, con
  * one workgroup per row and one lane per channel as the producing kernels do */
 int gi_debug_stat_acc_add(gi_ctx* ctx, unsigned long long* acc, int c, int reps, int group, int q, const float* addends,
                           int rows);
+/* The weight re-pack that runs after every update, on its own: `n` (1 .. 16) jobs, a HOST array, in ONE launch. Per job w is the fp32
+ * master [ca][16][cb]; packed (or NULL) receives T [ca][16][cb], phase (or NULL) T [4][cb][4][ca] as gi_pack_weights writes them;
+ * scale (or NULL): ca (scale_on_b = 0) or cb (1) fp32 factors multiplied in before the conversion (the inference-time BatchNorm
+ * fold). When every ca and cb is a multiple of 64 the 64 x 64-tile kernel runs (w, a per-b scale and both copies 16-byte aligned,
+ * fp16 copies 8-byte), else the 32 x 32-tile one. */
+typedef struct gi_pack_job {
+  const float* w; void* packed; void* phase;
+  int ca, cb, scale_on_b;
+  const float* scale;
+} gi_pack_job;
+int gi_debug_pack_weights_batch(gi_ctx* ctx, int dtype, const gi_pack_job* jobs, int n);
 /* ---- the PatchGAN critic head on its own (test seam) ------------------------------------------------------------------------
  * Conv2d(c,1,4,1,0) + Flatten + Linear(P,1) [+ Sigmoid] of csrc/head.hip, forward and backward; each entry checks what the kernels
  * assume (GI_ERR_INVALID before any launch) and forwards to the dispatcher the networks call; nothing here is on a training path.
