@@ -151,6 +151,8 @@ PROTOTYPES = {
     "gi_mask_bbox": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "gi_window_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gi_feather_paste": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "gi_mask_components_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "gi_mask_components": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gi_diffaug_params": (_i, [_vp, _i, _u64, _u64, _i, _i, _i, _vp]),
     "gi_diffaug_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "gi_diffaug_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -3,11 +3,13 @@
 
     python gan-inpainting_amd/inpaint.py -m runs/model/wgan_l1/epoch100_G.pt -i photo.png --mask hole.png -o out/
     python gan-inpainting_amd/inpaint.py -m epoch100_G.pt -i photos/ --masks freeform --mask-seed 3 -o out/ --panel
+    python gan-inpainting_amd/inpaint.py -m epoch100_G.pt -i scan.png --mask scratches.png -o out/ --windows per-hole
 
 -i names an image or a directory of images; --mask a mask file, or a directory holding a mask under each image's file name (a
 nonzero mask pixel is a hole); --masks rect|freeform draws the holes with the device mask generator instead (lib/data/masks.py,
 images of 16 .. 4096 pixels a side). Every picture is decoded to 8-bit grey like the training data, repaired at its own size and
-written as <outdir>/<name>.png; --panel adds <name>_panel.png: original | original with the hole blanked | result."""
+written as <outdir>/<name>.png; --windows per-hole repairs every group of holes in a window of its own and prints
+the holes and windows of each image; --panel adds <name>_panel.png: original | original with the hole blanked | result."""
 import argparse
 import os
 import sys
@@ -35,6 +37,10 @@ def build_parser():
     p.add_argument("--context", type=float, default=2.0, help="window side / hole side")
     p.add_argument("--feather", type=int, default=8, help="blend radius in pixels (0 .. 63; 0 = hard paste)")
     p.add_argument("--batchsize", type=int, default=16, help="windows per generator forward")
+    p.add_argument("--windows", choices=["single", "per-hole"], default="single",
+                   help="single: one window around all holes of an image; per-hole: one window per group of holes (connected components)")
+    p.add_argument("--max-holes", dest="max_holes", type=int, default=256,
+                   help="per-hole: an image with more components than this takes the single window (1 .. 65536)")
     p.add_argument("--panel", action="store_true", help="also write <name>_panel.png: original | hole blanked | result")
     return p
 
@@ -70,6 +76,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if (args.mask is None) == (args.masks is None):
         parser.error("give exactly one of --mask <file | directory> and --masks rect|freeform")
+    if not 1 <= args.max_holes <= 65536:
+        parser.error("--max-holes takes 1 .. 65536")
     if args.generator != "unet":
         raise NotImplementedError("HIP backend accelerates -g unet (the reference default, eval.py:29)")
     from gan_inpainting_amd import backend as B
@@ -100,7 +108,12 @@ def main(argv=None):
             m = DeviceMaskGenerator(args.masks, H, W, args.mask_seed)(torch.tensor([i], dtype=torch.int64))
             masks.append((m[0, 0] * 255).to(torch.uint8))
     net = load_generator(args.model, args.imagedim, args.dtype, device)
-    results = Inpainter(net, imagedim=args.imagedim, context=args.context, feather=args.feather, batch=args.batchsize)(images, masks)
+    inpainter = Inpainter(net, imagedim=args.imagedim, context=args.context, feather=args.feather, batch=args.batchsize,
+                          windows=args.windows, max_holes=args.max_holes)
+    results = inpainter(images, masks)
+    if args.windows == "per-hole":
+        for p, (holes, wins) in zip(paths, inpainter.holes):
+            print(f"{os.path.basename(p)}: {holes} holes, {wins} windows" + (" (more than --max-holes: single window)" if holes > args.max_holes else ""))
     os.makedirs(args.outdir, exist_ok=True)
     written = []
     for p, im, mk, res in zip(paths, images, masks, results):

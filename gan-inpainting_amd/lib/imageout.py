@@ -60,6 +60,29 @@ def mask_bbox(masks):
     return out
 
 
+MAX_COMPONENT_CAP = 65536
+
+
+def mask_components(mask, connectivity=8, cap=256):
+    """(H,W) uint8 mask -> (labels, count, table): labels (H,W) int32 on the device, -1 on background and on a hole pixel (byte
+    != 0) the smallest linear index of its 4- or 8-connected component; count, the number of components, a host int (the one
+    device -> host copy); table (min(count, cap), 6) int32 on the device, a row (label, y0, x0, y1, x1, area) per component in
+    label order, the box inclusive (csrc/components.hip)."""
+    mask = _need(mask, torch.uint8, "imageout.mask_components")
+    if mask.dim() != 2:
+        raise ValueError(f"mask_components takes one (H,W) mask, got {tuple(mask.shape)}")
+    H, W = mask.shape
+    cap = int(cap)
+    lib, dev = B.lib(), mask.device
+    labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    table = torch.empty((max(cap, 0), 6), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.gi_mask_components_workspace_bytes(H, W, cap)), 4), dtype=torch.uint8, device=dev)
+    B.check(lib.gi_mask_components(B.get_ctx(dev), B.ptr(mask), H, W, int(connectivity), cap, B.ptr(labels), B.ptr(count), B.ptr(table), B.ptr(ws)))
+    n = int(count.item())
+    return labels, n, table[:min(n, cap)]
+
+
 def window_crop(src, window, binarize=False, out=None):
     """The (wy, wx, wh, ww) window of a (H,W) uint8 image as a dense (wh, ww) tensor; binarize: nonzero -> 255."""
     src = _need(src, torch.uint8, "imageout.window_crop")
@@ -71,9 +94,11 @@ def window_crop(src, window, binarize=False, out=None):
     return out
 
 
-def feather_paste(orig, mask, window, patch, r):
+def feather_paste(orig, mask, window, patch, r, out=None):
     """A copy of `orig` (H,W) whose window holds the blend of `patch` (wh,ww) and `orig`: all patch on hole pixels (mask != 0), the
-    weight 2a / (2r+1)^2 elsewhere, a = the hole pixels in the (2r+1)^2 box inside the window (include/ganinpaint.h)."""
+    weight 2a / (2r+1)^2 elsewhere, a = the hole pixels in the (2r+1)^2 box inside the window (include/ganinpaint.h). out: a
+    (H,W) uint8 tensor that takes the window's bytes instead of a fresh copy (several disjoint windows of one picture paste into
+    one copy of it; the entry still reads `orig`)."""
     orig = _need(orig, torch.uint8, "imageout.feather_paste")
     mask = _need(mask, torch.uint8, "imageout.feather_paste")
     patch = _need(patch, torch.uint8, "imageout.feather_paste")
@@ -81,7 +106,12 @@ def feather_paste(orig, mask, window, patch, r):
     wy, wx, wh, ww = (int(v) for v in window)
     if mask.shape != orig.shape or tuple(patch.shape) != (wh, ww):
         raise ValueError(f"feather_paste: mask {tuple(mask.shape)} / patch {tuple(patch.shape)} do not fit image {(H, W)}, window {(wh, ww)}")
-    dst = orig.clone()
+    if out is None:
+        dst = orig.clone()
+    else:
+        dst = out
+        if not torch.is_tensor(dst) or dst.dtype != torch.uint8 or dst.device != orig.device or dst.shape != orig.shape or not dst.is_contiguous():
+            raise ValueError("feather_paste: out is a contiguous uint8 tensor of the image's shape on its device")
     B.check(B.lib().gi_feather_paste(B.get_ctx(orig.device), B.ptr(orig), B.ptr(mask), H, W, wy, wx, wh, ww, B.ptr(patch), int(r), B.ptr(dst)))
     return dst
 

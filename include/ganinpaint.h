@@ -571,6 +571,17 @@ int gi_window_crop(gi_ctx* ctx, const uint8_t* src, int H, int W, int wy, int wx
  * falls linearly from 1 to 0 at distance r + 1. */
 int gi_feather_paste(gi_ctx* ctx, const uint8_t* orig, const uint8_t* mask, int H, int W, int wy, int wx, int wh, int ww,
                      const uint8_t* patch, int r, uint8_t* dst);
+/* Connected components of a hole mask (tests/components_ref.py is the restatement, exact in every output). mask: (H, W)
+ * uint8, dense, any byte alignment, a byte != 0 is a hole pixel; connectivity 4 or 8; 1 <= cap <= 65536; H * W < 2^31 - 32.
+ * labels_out (H, W) int32: -1 on background, on a hole pixel the smallest linear index y * W + x of any pixel of its component;
+ * always complete, whatever cap is. count_out: one int, the true number of components, also when it exceeds cap. table_out
+ * (cap, 6) int32: row k < min(count, cap) = (label, y0, x0, y1, x1, area) of the component with the k-th smallest label, the box
+ * inclusive; the rows beyond are left untouched. workspace: gi_mask_components_workspace_bytes(H, W, cap) bytes on the device (0
+ * for arguments the entry refuses); it and the three outputs are 4-byte aligned. Integer atomics only: every output is a pure
+ * function of the mask, identical from run to run. */
+size_t gi_mask_components_workspace_bytes(int H, int W, int cap);
+int gi_mask_components(gi_ctx* ctx, const uint8_t* mask, int H, int W, int connectivity, int cap, int* labels_out, int* count_out,
+                       int* table_out, void* workspace);
 
 /* ---- batch assembly from a device-resident image store (lib/data/cache.py): store is (n_store,h,w) uint8 on
  *      the device, rows_dev n int64 on the device, out (n,h,w) of out_kind: 0 fp32 (float)v / 255.0f (the ToTensor quotient of
