@@ -20,15 +20,20 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
 __global__ void __launch_bounds__(256) eval_recon_partial_kernel(const float* __restrict__ ground, const float* __restrict__ gen,
                                                                  const float* __restrict__ m, int64_t count,
                                                                  float* __restrict__ out, double* __restrict__ partial) {
+  // every product below is rounded before it is added or subtracted, as in the reference. Without the pragma the composite compiles to
+  // one fused multiply-add (as mask_composite_kernel of elementwise.hip did), an ulp off the reference once the mask is fractional;
+  // __fadd_rn(__fmul_rn(..)) does not prevent that, with or without the pragma, so these are plain operators. The double sums take
+  // exact products either way.
+#pragma clang fp contract(off)
   __shared__ double sh[4];
   double s1 = 0.0, s2 = 0.0, l1 = 0.0, l2 = 0.0, cnt = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
     const float g = ground[i], mm = m[i];
     const float masked = g * (1.f - mm);
-    const float o = __fadd_rn(__fmul_rn(gen[i], mm), masked);   // mul, then add: two roundings like `out * m + masked`
+    const float o = gen[i] * mm + masked;   // mul, then add: two roundings like `out * m + masked`
     if (out) out[i] = o;
     const float d = g - o;
-    const float dl = __fsub_rn(__fmul_rn(o, mm), __fmul_rn(g, mm));   // loss(y*mask, yhat*mask): y = out, yhat = ground
+    const float dl = o * mm - g * mm;   // loss(y*mask, yhat*mask): y = out, yhat = ground
     s1 += (double)fabsf(d);
     s2 += (double)d * d;
     l1 += (double)fabsf(dl);
