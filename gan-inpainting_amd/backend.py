@@ -114,6 +114,15 @@ PROTOTYPES = {
     "gi_lpips_sync_weights": (_i, [_vp]),
     "gi_lpips_distance": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "gi_lpips_features": (_i, [_vp, _vp, _i, _i, _vp]),
+    "gi_lpips_grad_workspace_bytes": (_i64, [_vp]),
+    "gi_lpips_bind_grad": (_i, [_vp, _vp, _i64]),
+    "gi_lpips_distance_grad": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _f]),
+    "gi_lpips_grad_tap": (_i, [_vp, _i, _vp]),
+    "gi_debug_lpips_pack_t": (_i, [_vp, _vp, _vp, _i, _i]),
+    "gi_debug_lpips_seed": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gi_debug_lpips_scale": (_i, [_vp, _vp, _vp, _i]),
+    "gi_debug_lpips_act_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "gi_debug_lpips_conv1_adjoint": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i]),
     "gi_debug_lpips_conv1": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gi_debug_lpips_fold": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "gi_debug_lpips_tap_ws_bytes": (_i64, [_i]),

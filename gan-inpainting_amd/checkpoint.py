@@ -34,6 +34,8 @@ def compat_args(state, world, nets):
         out["diffaug_seed"] = int(state.get("diffaug_seed") or 0)
     if state.get("lpips_model") is not None:      # --lpips-weights: the evaluation records of the resumed run carry `lpips` too
         out["lpips"] = 1
+    if state.get("lpips_loss"):        # --lpips-loss: only when set, so states written without it keep their keys
+        out["lpips_loss"] = float(state["lpips_loss"])
     out["world_size"] = int(world)
     for name, net in nets.items():
         out[f"params/{name}"] = int(sum(p.numel() for p in net.parameters()))

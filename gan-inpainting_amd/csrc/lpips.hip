@@ -1,5 +1,6 @@
 // LPIPS (Zhang et al. 2018, `lpips` v0.1, net = 'vgg') between two batches of grey images: the learned perceptual distance the
-// inpainting papers report next to FID. A metric of the evaluation pass only: no backward.
+// inpainting papers report next to FID. The evaluation pass uses the forward alone; the opt-in backward w.r.t. `a` (second
+// half of this file) needs a second workspace, and a handle that never binds it runs launch for launch as without it.
 //
 // `a` and `b` run as ONE stacked batch of 2n images (NHWC fp16), as in vgg.hip:
 //   conv1_1  the network's input is alpha_c x + beta_c per channel (the scaling layer after normalize=True) of the grey image repeated
@@ -285,6 +286,247 @@ __global__ void __launch_bounds__(256) lpips_nhwc_to_nchw_kernel(const half_t* _
   }
 }
 
+// ================================================================================================================================
+// Opt-in backward: gscale * d d[i] / d a[i], b constant. As vgg.hip's the chain runs on s * gradient in fp16
+// with fp32 accumulation, but with ONE power of two s_i PER IMAGE: d[i] depends on a[i] alone and every kernel of the chain is linear
+// per image, so a nearly identical pair does not underflow next to a very different one and an image's bits do not depend on its
+// chunk-mates. No float atomics: the only atomic is an unsigned max over bit patterns of non-negative floats (order-independent).
+// ================================================================================================================================
+
+// [cout][cin][3][3] fp32 -> fp16 [cin][tap'][cout], tap' = 8 - tap: the transpose of a 3x3 / s1 / p1 convolution is that convolution with
+// the taps reversed and the channel roles exchanged, so the input-gradient GEMMs run on the forward's mode-2 kernels (vgg.hip's
+// pack3x3_t_kernel)
+__global__ void __launch_bounds__(256) lpips_pack3x3_t_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
+  const int64_t total = (int64_t)cin * 9 * cout;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int o = (int)(i % cout);
+    const int t = (int)((i / cout) % 9);
+    const int c = (int)(i / ((int64_t)cout * 9));
+    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + (8 - t)];
+  }
+}
+
+// Seed of one pixel: the gradient of d_l w.r.t. the post-ReLU vector a (b constant), in the tap kernel's lane layout. With ra = |a|,
+// ia = 1 / (ra + 1e-10), a^ = a ia, delta = a^ - b^ (the forward's rounded products: equal inputs give delta = 0 exactly) and
+// q = sum_c w_c delta_c a^_c:   seed_k = c2 ia (w_k delta_k - q a_k / ra),  c2 = 2 / HW;   ra == 0: seed = 0 (autograd gives NaN there,
+// but a post-ReLU vector is zero only where the ReLU mask below removes every channel anyway).
+template <int LPP>
+__device__ __forceinline__ void lp_seed_pixel(const h8_t a, const h8_t b, const float (&w)[8], float c2, float (&seed)[8]) {
+  float fa[8], fb[8], sa = 0.f, sb = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    fa[e] = (float)a[e];
+    fb[e] = (float)b[e];
+    sa = fmaf(fa[e], fa[e], sa);
+    sb = fmaf(fb[e], fb[e], sb);
+  }
+#pragma unroll
+  for (int off = LPP / 2; off > 0; off >>= 1) { sa += __shfl_xor(sa, off); sb += __shfl_xor(sb, off); }
+  const float ra = sqrtf(sa);
+  const float ia = 1.f / (ra + 1e-10f), ib = 1.f / (sqrtf(sb) + 1e-10f);
+  float pa[8], wd[8], q = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    pa[e] = fa[e] * ia;
+    wd[e] = w[e] * lp_unit_diff(fa[e], ia, fb[e], ib);
+    q = fmaf(wd[e], pa[e], q);
+  }
+#pragma unroll
+  for (int off = LPP / 2; off > 0; off >>= 1) q += __shfl_xor(q, off);
+  const bool live = ra > 0.f;
+  const float ir = live ? 1.f / ra : 0.f, k = live ? c2 * ia : 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) seed[e] = k * (wd[e] - q * (fa[e] * ir));
+}
+
+// One tap of n pairs, F as for lpips_tap_kernel, workgroup (x, i) over the pixels of pair i.
+//   STORE = false: smax[i] = max(smax[i], max |seed|) as a bit pattern (bit patterns of non-negative floats order like the floats);
+//   STORE = true:  sc[i] * seed in fp16 OVER the b half of the map: a lane overwrites the eight elements of b it has just read, and
+//                  nothing else reads that half after the forward.
+struct LpSeedP {
+  half_t* F; const float* lin; unsigned* smax; const float* sc;
+  int n, HW; float c2;
+};
+template <int LPP, bool STORE>
+__global__ void __launch_bounds__(256) lpips_seed_kernel(LpSeedP p) {
+  constexpr int C = LPP * 8, UPB = 256 / LPP;
+  __shared__ float red[4];
+  const int img = blockIdx.y;
+  const int sub = threadIdx.x % LPP, grp = threadIdx.x / LPP;
+  const half_t* Fa = p.F + (int64_t)img * p.HW * C + sub * 8;
+  half_t* Fb = p.F + (int64_t)(img + p.n) * p.HW * C + sub * 8;
+  float w[8];
+  {
+    const f4_t w0 = *(const f4_t*)(p.lin + sub * 8), w1 = *(const f4_t*)(p.lin + sub * 8 + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { w[e] = w0[e]; w[4 + e] = w1[e]; }
+  }
+  const float s = STORE ? p.sc[img] : 1.f;
+  float m = 0.f;
+  // every lane of a group takes part in the butterflies: the loop bound is the same for all lanes of a group
+  for (int u = blockIdx.x * UPB + grp; u < p.HW; u += gridDim.x * UPB) {
+    const h8_t a = *(const h8_t*)(Fa + (int64_t)u * C), b = *(const h8_t*)(Fb + (int64_t)u * C);
+    float seed[8];
+    lp_seed_pixel<LPP>(a, b, w, p.c2, seed);
+    if constexpr (STORE) {
+      h8_t o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (half_t)(seed[e] * s);
+      *(h8_t*)(Fb + (int64_t)u * C) = o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(seed[e]));
+    }
+  }
+  if constexpr (!STORE) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+      if (m > 0.f) atomicMax(p.smax + img, __float_as_uint(m));
+    }
+  }
+}
+
+// Image i: s_i = 2^(kLpSeedExp - e) with its largest seed over the five taps m 2^e, m in [0.5, 1): the largest scaled seed lands in
+// [2^(kLpSeedExp - 1), 2^kLpSeedExp). All seeds zero (a[i] == b[i]) or a non-finite maximum: s_i = 1. sc[i] = s_i, sc[n + i] = 1 / s_i.
+// kLpSeedExp = -2: headroom as derived in DESIGN 4.13.
+constexpr int kLpSeedExp = -2;
+__global__ void __launch_bounds__(64) lpips_scale_kernel(const unsigned* __restrict__ smax, float* __restrict__ sc, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const float am = __uint_as_float(smax[i]);
+  int ex = 0;
+  float s = 1.f;
+  if (am > 0.f && am < INFINITY) {
+    (void)frexpf(am, &ex);
+    int k = kLpSeedExp - ex;
+    k = k > 100 ? 100 : (k < -100 ? -100 : k);
+    s = ldexpf(1.f, k);
+  }
+  sc[i] = s;
+  sc[n + i] = 1.f / s;
+}
+
+// Activation backward between two input-gradient GEMMs, 16-byte NHWC accesses, 8 channels per thread; one fp16 rounding of the fp32 sum:
+//   POOL = false: out = [act > 0] * (g + seed)                        (g and / or seed may be null; out may alias g)
+//   POOL = true:  g lives on the (H/2, W/2) grid: every 2x2 window of `act` routes its value to the first maximum in row-major order
+//                 (F.max_pool2d's backward; the arg-max is recomputed from the kept map), then out = [act > 0] * (routed g + seed) at all
+//                 four positions (seed may be null). The taps of this network are the pooled layers, so the seed joins here.
+// relu = 0 drops the [act > 0] factor: the gradient w.r.t. the post-ReLU map itself (gi_lpips_grad_tap).
+template <bool POOL>
+__global__ void __launch_bounds__(256) lpips_act_bwd_kernel(const half_t* g, const half_t* __restrict__ act, const half_t* __restrict__ seed,
+                                                            half_t* out, int nimg, int H, int W, int C, int relu) {
+  const int cg = C / 8;
+  const h8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (!POOL) {
+    const int64_t total = (int64_t)nimg * H * W * cg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+      const h8_t a = *(const h8_t*)(act + i * 8);
+      const h8_t gv = g ? *(const h8_t*)(g + i * 8) : z8;
+      const h8_t sv = seed ? *(const h8_t*)(seed + i * 8) : z8;
+      h8_t o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (!relu || (float)a[e] > 0.f) ? (half_t)((float)gv[e] + (float)sv[e]) : (half_t)0.f;
+      *(h8_t*)(out + i * 8) = o;
+    }
+  } else {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t total = (int64_t)nimg * Ho * Wo * cg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+      const int gq = (int)(i % cg);
+      const int64_t pq = i / cg;
+      const int x = (int)(pq % Wo);
+      const int64_t tt = pq / Wo;
+      const int y = (int)(tt % Ho);
+      const int64_t img = tt / Ho;
+      const int64_t o00 = (((img * H + 2 * y) * W + 2 * x) * (int64_t)C) + gq * 8;
+      const int64_t off[4] = {o00, o00 + C, o00 + (int64_t)W * C, o00 + (int64_t)W * C + C};
+      h8_t a[4], sv[4], o[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { a[q] = *(const h8_t*)(act + off[q]); sv[q] = seed ? *(const h8_t*)(seed + off[q]) : z8; }
+      const h8_t gv = *(const h8_t*)(g + pq * C + gq * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        int best = 0;
+        float bv = (float)a[0][e];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) { const float av = (float)a[q][e]; if (av > bv) { bv = av; best = q; } }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float val = (q == best ? (float)gv[e] : 0.f) + (float)sv[q][e];
+          o[q][e] = (!relu || (float)a[q][e] > 0.f) ? (half_t)val : (half_t)0.f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *(h8_t*)(out + off[q]) = o[q];
+    }
+  }
+}
+
+// First-layer adjoint: dimg[i][y][x] = mul_i * sum_{ky,kx,o} wA[o][ky][kx] * D[i][y+1-ky][x+1-kx][o] in fp32, wA the folded image-plane
+// weights (the indicator plane is constant and contributes nothing), mul_i = gscale / s_i from device memory: the fp16 scale leaves
+// here. vgg_conv1_adjoint_kernel's tiling: a workgroup owns 16 x 32 pixels, reduces the 64 channels of each of the 18 x 34 halo pixels
+// of D to nine per-tap sums in LDS (one pass over D in 16-byte loads), then every output pixel adds its nine neighbours' sums.
+__global__ void __launch_bounds__(256) lpips_conv1_adjoint_kernel(const half_t* __restrict__ D, const float* __restrict__ wA, const float* __restrict__ sc_inv,
+                                                                  float gscale, float* __restrict__ dimg, int H, int W) {
+  constexpr int TH = 16, TW = 32, HH = TH + 2, HW_ = TW + 2, NH = HH * HW_;
+  __shared__ float T[NH * 9];
+  const int img = blockIdx.z, y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
+  const half_t* Di = D + (int64_t)img * H * W * 64;
+  for (int h = threadIdx.x; h < NH; h += 256) {
+    const int hy = h / HW_, hx = h - hy * HW_;
+    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
+    float t[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t[k] = 0.f;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      const half_t* src = Di + ((int64_t)y * W + x) * 64;
+      h8_t v[8];
+#pragma unroll
+      for (int c8 = 0; c8 < 8; ++c8) v[c8] = *(const h8_t*)(src + c8 * 8);
+#pragma unroll
+      for (int c8 = 0; c8 < 8; ++c8)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = (float)v[c8][e];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) t[k] = fmaf(wA[(c8 * 8 + e) * 9 + k], d, t[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) T[h * 9 + k] = t[k];
+  }
+  __syncthreads();
+  const float mul = gscale * sc_inv[img];
+  for (int o = threadIdx.x; o < TH * TW; o += 256) {
+    const int ty = o / TW, tx = o - ty * TW;
+    const int y = y0 + ty, x = x0 + tx;
+    if (y >= H || x >= W) continue;
+    float s = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) s += T[((ty + 2 - ky) * HW_ + (tx + 2 - kx)) * 9 + ky * 3 + kx];
+    dimg[((int64_t)img * H + y) * W + x] = s * mul;
+  }
+}
+
+// NHWC fp16 (s_i * gradient) -> NCHW fp32 gradient (gi_lpips_grad_tap)
+__global__ void __launch_bounds__(256) lpips_nhwc_to_nchw_unscale_kernel(const half_t* __restrict__ in, const float* __restrict__ sc_inv,
+                                                                         float* __restrict__ out, int nimg, int HW, int C) {
+  const int64_t total = (int64_t)nimg * HW * C;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int px = (int)(i % HW);
+    const int64_t t = i / HW;
+    const int c = (int)(t % C);
+    const int64_t img = t / C;
+    out[i] = (float)in[(img * HW + px) * C + c] * sc_inv[img];
+  }
+}
+
 // ---- host launch code: one copy of every grid rule, shared by the runner and the gi_debug_lpips_* entries -----------------------------
 
 int lp_pack3x3(hipStream_t st, const float* w, half_t* out, int cout, int cin) {
@@ -348,6 +590,71 @@ int lp_finish(hipStream_t st, const double* partial, const LpFinP& f, float* out
   return GI_OK;
 }
 
+// ---- the backward's launch code ------------------------------------------------------------------------------------------------------
+int lp_pack3x3_t(hipStream_t st, const float* w, half_t* out, int cout, int cin) {
+  hipLaunchKernelGGL(lpips_pack3x3_t_kernel, dim3(grid_for((int64_t)cout * 9 * cin, 256, 2048)), dim3(256), 0, st, w, out, cout, cin);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// one pass of a tap's seed over n pairs (F [2n][HW][C]): store = false: smax[i] = max |seed| of pair i; store = true: sc[i] * seed over the b half
+int lp_seed(hipStream_t st, bool store, half_t* F, int n, int64_t HW, int C, const float* lin, unsigned* smax, const float* sc) {
+  LpSeedP p;
+  p.F = F; p.lin = lin; p.smax = smax; p.sc = sc; p.n = n; p.HW = (int)HW; p.c2 = (float)(2.0 / (double)HW);
+  const dim3 grid(grid_for(HW, 256 / (C / 8), LP_MAXNB), n);
+#define LP_SEED_CASE(LPP)                                                                            \
+  case LPP * 8:                                                                                      \
+    if (store) hipLaunchKernelGGL((lpips_seed_kernel<LPP, true>), grid, dim3(256), 0, st, p);        \
+    else hipLaunchKernelGGL((lpips_seed_kernel<LPP, false>), grid, dim3(256), 0, st, p);             \
+    break;
+  switch (C) {
+    LP_SEED_CASE(8)
+    LP_SEED_CASE(16)
+    LP_SEED_CASE(32)
+    LP_SEED_CASE(64)
+    default: gi_set_error("lpips seed: C=%d (64, 128, 256 or 512)", C); return GI_ERR_INVALID;
+  }
+#undef LP_SEED_CASE
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int lp_scale(hipStream_t st, const unsigned* smax, float* sc, int n) {
+  hipLaunchKernelGGL(lpips_scale_kernel, dim3((n + 63) / 64), dim3(64), 0, st, smax, sc, n);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int lp_act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
+  if (pool) {
+    hipLaunchKernelGGL(lpips_act_bwd_kernel<true>, dim3(grid_for((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out,
+                       n, H, W, C, relu);
+  } else {
+    hipLaunchKernelGGL(lpips_act_bwd_kernel<false>, dim3(grid_for((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C,
+                       relu);
+  }
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+int lp_conv1_adjoint(hipStream_t st, const half_t* D, const float* wA, const float* sc_inv, float gscale, float* dimg, int n, int H, int W) {
+  hipLaunchKernelGGL(lpips_conv1_adjoint_kernel, dim3((W + 31) / 32, (H + 15) / 16, n), dim3(256), 0, st, D, wA, sc_inv, gscale, dimg, H, W);
+  GI_LAUNCH_CHECK();
+  return GI_OK;
+}
+// one input-gradient GEMM: the transposed 3x3 convolution (weights from lp_pack3x3_t) of n gradient maps, no bias, no activation; mask:
+// the ReLU mask of the result's layer in the epilogue, where the dispatched kernel has one (applied: whether it had)
+int lp_conv3x3_bwd(hipStream_t st, const half_t* in, const half_t* wT, half_t* out, int n, int H, int W, int cin, int cout, const half_t* mask, int* applied) {
+  IgemmArgs a = IgemmArgs{};
+  a.in = in; a.w = wT; a.out = out;
+  a.bias = nullptr; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
+  a.n = n; a.Hs = H; a.Ws = W;
+  a.cin = cin; a.ldin = cin; a.coffin = 0;
+  a.cout = cout; a.ldout = cout; a.coffout = 0;
+  a.relu_in = 0; a.relu_cend = 0; a.act_out = GI_ACT_NONE; a.force_splitk = 0;
+  if (mask) { a.mask = mask; a.ldmask = cout; a.coffmask = 0; a.mask_slope = 0.f; a.add = nullptr; a.ldadd = cout; a.coffadd = 0; }
+  const int rc = op_igemm(st, GI_F16, 2, a);
+  if (rc == GI_ERR_UNSUPPORTED) gi_set_error("lpips backward: no mode-2 kernel serves n=%d %dx%d %d->%d", n, H, W, cin, cout);
+  *applied = mask && a.mask_applied;
+  return rc;
+}
+
 }  // namespace
 
 struct gi_lpips {
@@ -364,6 +671,17 @@ struct gi_lpips {
   float* wB;              //                                 indicator plane
   double* partial;        // [5 taps][max_pairs][LP_MAXNB]
   bool bound, synced;
+  // opt-in backward (gi_lpips_bind_grad): a separate workspace; a handle that never binds it runs exactly as before
+  char* gws;
+  int64_t gws_bytes;
+  bool gbound;
+  int grad_n;             // pairs of the last grad call (0: none yet): gi_lpips_grad_tap replays its backward
+  half_t* ga[NCONV];      // post-ReLU maps, [a half | b half]; the b half survives only at the taps (where the seeds replace it)
+  half_t* gpool[NCONV];   // 2x2 max pool after the four pooled taps (both halves): the next layer's input
+  half_t* wT[NCONV];      // [1..12] fp16 weights of the transposed convolutions: [cin][reversed tap][cout]
+  half_t* gbuf[2];        // gradient ping-pong (n images)
+  unsigned* smax;         // [max_pairs] largest |seed| of an image over the five taps (bit patterns of non-negative floats)
+  float* sc;              // [i] = s_i = 2^k, [n + i] = 1 / s_i: image i's backward runs on s_i * gradient
 };
 
 namespace {
@@ -382,42 +700,148 @@ int64_t lpips_ws_layout(gi_lpips* v, char* base) {
   return off;
 }
 
+// grad workspace (vgg.hip's arena scheme). The forward's maps go to two arenas, alternating per stage (convolution or pooled tap): a stage
+// reads the other arena and writes [a half | b half] behind what its arena must keep - the a halves of the 13 convolutions (ReLU masks,
+// pool routing) and both halves at the five taps - so a b half nobody needs is overwritten by the stage after next.
+int64_t lpips_gws_layout(gi_lpips* v, char* base) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
+  int64_t pos[2] = {0, 0}, ext[2] = {0, 0}, start[2 * NCONV];
+  int H = v->H, W = v->W, k = 0;
+  for (int i = 0; i < NCONV; ++i) {
+    const int64_t half = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
+    start[2 * i] = pos[k & 1];
+    if (start[2 * i] + 2 * half > ext[k & 1]) ext[k & 1] = start[2 * i] + 2 * half;
+    pos[k & 1] += half * (kTapAfter[i] >= 0 ? 2 : 1);
+    ++k;
+    start[2 * i + 1] = -1;
+    if (kTapAfter[i] >= 0 && kTapAfter[i] < NTAP - 1) {
+      H /= 2; W /= 2;
+      start[2 * i + 1] = pos[k & 1];       // kept by nobody: the next stage of this arena starts at the same place
+      const int64_t ph = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
+      if (start[2 * i + 1] + 2 * ph > ext[k & 1]) ext[k & 1] = start[2 * i + 1] + 2 * ph;
+      ++k;
+    }
+  }
+  char* arena[2];
+  arena[0] = take(ext[0]);
+  arena[1] = take(ext[1]);
+  for (int i = 0, kk = 0; i < NCONV; ++i) {
+    v->ga[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i]) : nullptr;
+    ++kk;
+    v->gpool[i] = nullptr;
+    if (start[2 * i + 1] >= 0) { v->gpool[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i + 1]) : nullptr; ++kk; }
+  }
+  v->wT[0] = nullptr;
+  for (int i = 1; i < NCONV; ++i) v->wT[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
+  const int64_t gbytes = (int64_t)v->max_pairs * v->H * v->W * 64 * 2;
+  v->gbuf[0] = (half_t*)take(gbytes);
+  v->gbuf[1] = (half_t*)take(gbytes);
+  v->smax = (unsigned*)take((int64_t)v->max_pairs * 4);
+  v->sc = (float*)take((int64_t)2 * v->max_pairs * 4);
+  return off;
+}
+
 // the network on 2n stacked images; the taps leave their partials behind (fin: their counts). feat_out: stop at tap stop_tap and return
-// its map of the first n images as NCHW fp32
-int lpips_run(gi_lpips* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out, LpFinP& fin) {
+// its map of the first n images as NCHW fp32. grad: the same launches, but every stage writes its own map in the grad workspace (nothing
+// the backward reads is overwritten)
+int lpips_run(gi_lpips* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out, LpFinP& fin, bool grad = false) {
   hipStream_t st = v->ctx->stream;
   const int nimg = 2 * n;
   int H = v->H, W = v->W, cur = 0;
+  half_t* curp = grad ? v->ga[0] : v->act[0];
   // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of gi_lpips_create)
-  GI_TRY(lp_conv1(st, xa, xb, n, H, W, v->wA, v->wB, v->params + v->boff[0], v->act[0]));
+  GI_TRY(lp_conv1(st, xa, xb, n, H, W, v->wA, v->wB, v->params + v->boff[0], curp));
   for (int i = 1; i < NCONV; ++i) {
-    GI_TRY(lp_conv3x3(st, v->act[cur], v->wpk[i], v->act[cur ^ 1], nimg, H, W, kCin[i], kCout[i], v->params + v->boff[i]));
+    half_t* outp = grad ? v->ga[i] : v->act[cur ^ 1];
+    GI_TRY(lp_conv3x3(st, curp, v->wpk[i], outp, nimg, H, W, kCin[i], kCout[i], v->params + v->boff[i]));
     cur ^= 1;
+    curp = outp;
     const int tap = kTapAfter[i], C = kCout[i];
     if (tap < 0) continue;
     if (feat_out && tap == stop_tap) {
-      hipLaunchKernelGGL(lpips_nhwc_to_nchw_kernel, dim3(grid_for((int64_t)n * H * W * C, 256, 4096)), dim3(256), 0, st, v->act[cur], feat_out, n, H * W, C);
+      hipLaunchKernelGGL(lpips_nhwc_to_nchw_kernel, dim3(grid_for((int64_t)n * H * W * C, 256, 4096)), dim3(256), 0, st, curp, feat_out, n, H * W, C);
       GI_LAUNCH_CHECK();
       return GI_OK;
     }
     const bool pool = tap < NTAP - 1;
+    half_t* poolp = pool ? (grad ? v->gpool[i] : v->act[cur ^ 1]) : nullptr;
     double* partial = v->partial + (int64_t)tap * v->max_pairs * LP_MAXNB;
     fin.inv[tap] = 1.0 / ((double)H * W);
 #ifdef GI_LPIPS_UNFUSED
     fin.nb[tap] = lp_tap_blocks(H, W, C, false);
-    GI_TRY(lp_tap(st, v->act[cur], n, H, W, C, v->params + v->linoff[tap], nullptr, partial));
+    GI_TRY(lp_tap(st, curp, n, H, W, C, v->params + v->linoff[tap], nullptr, partial));
     if (pool) {
-      hipLaunchKernelGGL(lpips_maxpool2_kernel, dim3(grid_for((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, v->act[cur],
-                         v->act[cur ^ 1], nimg, H / 2, W / 2, C);
+      hipLaunchKernelGGL(lpips_maxpool2_kernel, dim3(grid_for((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, curp, poolp, nimg,
+                         H / 2, W / 2, C);
       GI_LAUNCH_CHECK();
     }
 #else
     fin.nb[tap] = lp_tap_blocks(H, W, C, pool);
-    GI_TRY(lp_tap(st, v->act[cur], n, H, W, C, v->params + v->linoff[tap], pool ? v->act[cur ^ 1] : nullptr, partial));
+    GI_TRY(lp_tap(st, curp, n, H, W, C, v->params + v->linoff[tap], poolp, partial));
 #endif
-    if (pool) { cur ^= 1; H /= 2; W /= 2; }
+    if (pool) { cur ^= 1; curp = poolp; H /= 2; W /= 2; }
   }
   return GI_OK;
+}
+
+// seeds of the five taps from the maps the grad forward left: every image's maximum, then its s_i, then s_i * seed over the b halves
+int lpips_seeds(gi_lpips* v, int n) {
+  hipStream_t st = v->ctx->stream;
+  for (int pass = 0; pass < 2; ++pass) {
+    int H = v->H, W = v->W;
+    for (int i = 0; i < NCONV; ++i) {
+      const int tap = kTapAfter[i];
+      if (tap < 0) continue;
+      GI_TRY(lp_seed(st, pass == 1, v->ga[i], n, (int64_t)H * W, kCout[i], v->params + v->linoff[tap], v->smax, v->sc));
+      if (tap < NTAP - 1) { H /= 2; W /= 2; }
+    }
+    if (pass == 0) GI_TRY(lp_scale(st, v->smax, v->sc, n));
+  }
+  return GI_OK;
+}
+
+// The chain from conv5_3 down. D_l = s_i * gradient w.r.t. the PRE-activation of layer l = [a_l > 0] * (transposed conv of D_(l+1), un-pooled
+// where a pool sits between, + s_i * seed_l at a tap). stop_tap < 0: down to D_0, then the first-layer adjoint into grad_out. stop_tap = t:
+// the gradient w.r.t. the post-ReLU map of tap t (no [a > 0] factor) goes to tap_out as NCHW fp32, de-scaled.
+int lpips_backward(gi_lpips* v, int n, int stop_tap, float* tap_out, float* grad_out, float gscale) {
+  hipStream_t st = v->ctx->stream;
+  int Hl[NCONV], Wl[NCONV], stop = -1;
+  {
+    int H = v->H, W = v->W;
+    for (int i = 0; i < NCONV; ++i) {
+      Hl[i] = H; Wl[i] = W;
+      if (kTapAfter[i] >= 0 && kTapAfter[i] == stop_tap) stop = i;
+      if (kTapAfter[i] >= 0 && kTapAfter[i] < NTAP - 1) { H /= 2; W /= 2; }
+    }
+  }
+  const float* sc_inv = v->sc + n;
+  auto seed_of = [&](int l) -> const half_t* { return kTapAfter[l] >= 0 ? v->ga[l] + (int64_t)n * Hl[l] * Wl[l] * kCout[l] : nullptr; };
+  auto readback = [&](const half_t* g, int l) -> int {
+    hipLaunchKernelGGL(lpips_nhwc_to_nchw_unscale_kernel, dim3(grid_for((int64_t)n * Hl[l] * Wl[l] * kCout[l], 256, 4096)), dim3(256), 0, st, g, sc_inv,
+                       tap_out, n, Hl[l] * Wl[l], kCout[l]);
+    GI_LAUNCH_CHECK();
+    return GI_OK;
+  };
+  int cur = 0;
+  const int top = NCONV - 1;
+  GI_TRY(lp_act_bwd(st, false, nullptr, v->ga[top], seed_of(top), v->gbuf[cur], n, Hl[top], Wl[top], kCout[top], stop != top));
+  if (stop == top) return readback(v->gbuf[cur], top);
+  for (int l = top; l >= 1; --l) {
+    const int below = l - 1;
+    const bool pool = kTapAfter[below] >= 0, last = stop == below;      // below < top: a tap below the top is a pooled layer
+    int applied = 0;
+    // the ReLU mask of the layer below in the GEMM epilogue, where the dispatched kernel has one
+    GI_TRY(lp_conv3x3_bwd(st, v->gbuf[cur], v->wT[l], v->gbuf[cur ^ 1], n, Hl[l], Wl[l], kCout[l], kCin[l], pool ? nullptr : v->ga[below], &applied));
+    if (pool) {
+      GI_TRY(lp_act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], seed_of(below), v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
+    } else {
+      cur ^= 1;
+      if (!applied) GI_TRY(lp_act_bwd(st, false, v->gbuf[cur], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], 1));
+    }
+    if (last) return readback(v->gbuf[cur], below);
+  }
+  return lp_conv1_adjoint(st, v->gbuf[cur], v->wA, sc_inv, gscale, grad_out, n, v->H, v->W);
 }
 
 }  // namespace
@@ -442,6 +866,8 @@ int gi_lpips_create(gi_ctx* ctx, int H, int W, int max_pairs, gi_lpips** out) {
   v->param_floats = off;
   v->params = nullptr; v->ws = nullptr; v->bound = false; v->synced = false;
   v->ws_bytes = lpips_ws_layout(v, nullptr);
+  v->gws = nullptr; v->gbound = false; v->grad_n = 0;
+  v->gws_bytes = lpips_gws_layout(v, nullptr);
   *out = v;
   return GI_OK;
 }
@@ -489,6 +915,8 @@ int gi_lpips_sync_weights(gi_lpips* v) {
   hipStream_t st = v->ctx->stream;
   GI_TRY(lp_fold(st, v->params + v->woff[0], v->params + v->shiftoff, v->params + v->scaleoff, v->wA, v->wB));
   for (int i = 1; i < NCONV; ++i) GI_TRY(lp_pack3x3(st, v->params + v->woff[i], v->wpk[i], kCout[i], kCin[i]));
+  if (v->gbound)
+    for (int i = 1; i < NCONV; ++i) GI_TRY(lp_pack3x3_t(st, v->params + v->woff[i], v->wT[i], kCout[i], kCin[i]));
   v->synced = true;
   return GI_OK;
 }
@@ -500,6 +928,43 @@ int gi_lpips_distance(gi_lpips* v, const float* a, const float* b, int n, float*
   fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->max_pairs;
   GI_TRY(lpips_run(v, a, b, n, -1, nullptr, fin));
   return lp_finish(v->ctx->stream, v->partial, fin, out_n, per_layer_5n);
+}
+
+int64_t gi_lpips_grad_workspace_bytes(const gi_lpips* v) { return v ? v->gws_bytes : -1; }
+
+int gi_lpips_bind_grad(gi_lpips* v, void* ws, int64_t ws_bytes) {
+  GI_REQUIRE(v && ws, "lpips_bind_grad: null argument");
+  GI_REQUIRE(v->bound, "lpips_bind_grad: gi_lpips_bind first");
+  GI_REQUIRE(ws_bytes >= v->gws_bytes && ((uintptr_t)ws & 255) == 0, "lpips_bind_grad: workspace %lld bytes (need %lld, 256-byte aligned)",
+             (long long)ws_bytes, (long long)v->gws_bytes);
+  v->gws = (char*)ws;
+  lpips_gws_layout(v, v->gws);
+  v->gbound = true; v->synced = false; v->grad_n = 0;      // sync_weights packs the transposed weights
+  return GI_OK;
+}
+
+int gi_lpips_distance_grad(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n, float* grad_a, float gscale) {
+  GI_REQUIRE(v && v->gbound, "lpips_distance_grad: no grad workspace bound (gi_lpips_bind_grad)");
+  GI_REQUIRE(v->bound && v->synced, "lpips_distance_grad: bind + sync_weights first");
+  GI_REQUIRE(a && b && out_n && grad_a && n > 0 && n <= v->max_pairs, "lpips_distance_grad: n=%d (max %d)", n, v->max_pairs);
+  hipStream_t st = v->ctx->stream;
+  v->grad_n = 0;
+  GI_HIP(hipMemsetAsync(v->smax, 0, (size_t)v->max_pairs * 4, st));
+  LpFinP fin = {};
+  fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->max_pairs;
+  GI_TRY(lpips_run(v, a, b, n, -1, nullptr, fin, true));
+  GI_TRY(lp_finish(st, v->partial, fin, out_n, per_layer_5n));
+  GI_TRY(lpips_seeds(v, n));
+  v->grad_n = n;
+  return lpips_backward(v, n, -1, nullptr, grad_a, gscale);
+}
+
+int gi_lpips_grad_tap(gi_lpips* v, int tap, float* out_nchw_f32) {
+  GI_REQUIRE(v && v->gbound, "lpips_grad_tap: no grad workspace bound (gi_lpips_bind_grad)");
+  GI_REQUIRE(v->synced && v->grad_n > 0, "lpips_grad_tap: no gi_lpips_distance_grad call to read back");
+  GI_REQUIRE(out_nchw_f32 && tap >= 0 && tap < NTAP, "lpips_grad_tap: tap=%d", tap);
+  // replays the backward of the last grad call from what it left in the workspace (maps, seeds, scales), down to the tap
+  return lpips_backward(v, v->grad_n, tap, out_nchw_f32, nullptr, 1.f);
 }
 
 int gi_lpips_features(gi_lpips* v, const float* x, int n, int tap, float* out_nchw) {
@@ -544,6 +1009,43 @@ int gi_debug_lpips_tap(gi_ctx* ctx, const void* F, int n, int H, int W, int C, c
   fin.nb[0] = lp_tap_blocks(H, W, C, pooled != nullptr);
   fin.inv[0] = 1.0 / ((double)H * W);
   return lp_finish(st, (const double*)ws, fin, nullptr, d_n);
+}
+
+// ---- the backward's kernels one at a time ------------------------------------------------------------------------------------------------
+int gi_debug_lpips_pack_t(gi_ctx* ctx, const float* w, void* out, int cout, int cin) {
+  GI_REQUIRE(ctx && w && out, "debug_lpips_pack_t: null pointer");
+  GI_REQUIRE(cout > 0 && cin > 0 && GI_LP_FITS31((int64_t)cout * 9 * cin), "debug_lpips_pack_t: cout=%d cin=%d", cout, cin);
+  return lp_pack3x3_t(ctx->stream, w, (half_t*)out, cout, cin);
+}
+
+int gi_debug_lpips_seed(gi_ctx* ctx, int store, void* F, int n, int HW, int C, const float* lin, unsigned* smax, const float* sc) {
+  GI_REQUIRE(ctx && F && lin && (store ? sc != nullptr : smax != nullptr), "debug_lpips_seed: null pointer");
+  GI_REQUIRE(n > 0 && HW > 0 && (C == 64 || C == 128 || C == 256 || C == 512), "debug_lpips_seed: n=%d HW=%d C=%d (64, 128, 256 or 512)", n, HW, C);
+  GI_REQUIRE(GI_LP_FITS31((int64_t)2 * n * HW * C), "debug_lpips_seed: tensor beyond 32-bit offsets");
+  GI_REQUIRE(((uintptr_t)F & 15) == 0 && ((uintptr_t)lin & 15) == 0, "debug_lpips_seed: F and lin must be 16-byte aligned");
+  return lp_seed(ctx->stream, store != 0, (half_t*)F, n, HW, C, lin, smax, sc);
+}
+
+int gi_debug_lpips_scale(gi_ctx* ctx, const unsigned* smax, float* sc, int n) {
+  GI_REQUIRE(ctx && smax && sc && n > 0, "debug_lpips_scale: null pointer or n=%d", n);
+  return lp_scale(ctx->stream, smax, sc, n);
+}
+
+int gi_debug_lpips_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W, int C, int relu) {
+  GI_REQUIRE(ctx && act && out, "debug_lpips_act_bwd: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "debug_lpips_act_bwd: n=%d H=%d W=%d C=%d (C: a multiple of 8)", n, H, W, C);
+  GI_REQUIRE(GI_LP_FITS31((int64_t)n * H * W * C), "debug_lpips_act_bwd: tensor beyond 32-bit offsets");
+  GI_REQUIRE(!pool || (g && out != g && H % 2 == 0 && W % 2 == 0), "debug_lpips_act_bwd: the pool form needs g, out apart from g and even H=%d W=%d", H, W);
+  GI_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)act & 15) == 0 && ((uintptr_t)seed & 15) == 0 && ((uintptr_t)out & 15) == 0,
+             "debug_lpips_act_bwd: g, act, seed and out must be 16-byte aligned");
+  return lp_act_bwd(ctx->stream, pool != 0, (const half_t*)g, (const half_t*)act, (const half_t*)seed, (half_t*)out, n, H, W, C, relu);
+}
+
+int gi_debug_lpips_conv1_adjoint(gi_ctx* ctx, const void* D, const float* wA, const float* sc_inv, float gscale, float* dimg, int n, int H, int W) {
+  GI_REQUIRE(ctx && D && wA && sc_inv && dimg, "debug_lpips_conv1_adjoint: null pointer");
+  GI_REQUIRE(n > 0 && H > 0 && W > 0 && GI_LP_FITS31((int64_t)n * H * W * 64), "debug_lpips_conv1_adjoint: n=%d H=%d W=%d", n, H, W);
+  GI_REQUIRE(((uintptr_t)D & 15) == 0, "debug_lpips_conv1_adjoint: D must be 16-byte aligned");
+  return lp_conv1_adjoint(ctx->stream, (const half_t*)D, wA, sc_inv, gscale, dimg, n, H, W);
 }
 
 }  // extern "C"

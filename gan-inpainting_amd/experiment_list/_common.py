@@ -176,6 +176,25 @@ def make_ema(state, net_G):
     return optim.EMA(net_G, decay) if decay > 0 else None
 
 
+def lpips_loss_kw(state):
+    """The opt-in LPIPS generator term of the WGAN steps (train.py --lpips-loss W): {lpips, lpips_weight} from state['lpips_model'] (the
+    LPIPS(grad=True) object that also serves the metric) and state['lpips_loss']; {} when off."""
+    w = float(state.get("lpips_loss") or 0.0)
+    if not w:
+        return {}
+    model = state.get("lpips_model")
+    if model is None or not getattr(model, "grad", False):
+        raise ValueError("--lpips-loss needs --lpips-weights (an LPIPS(grad=True) model in state['lpips_model'])")
+    return {"lpips": model, "lpips_weight": w}
+
+
+def refuse_lpips_loss(state, name):
+    """Plugins whose step has no oracle-pinned hook for an extra generator term."""
+    if float(state.get("lpips_loss") or 0.0):
+        raise ValueError(f"--lpips-loss is not defined for {name}: only the WGAN plugins (wgan_l1, wgan_rmse, "
+                         "wgan_perceptual_style_faceparsing) take the term (DESIGN.md 4.13)")
+
+
 def make_diffaug(state):
     """lib.models.augment.DiffAugment of state['diffaug'] / state['diffaug_seed'] (train.py --diffaug, --diffaug-seed), else None.
     Only the step object takes it: the evaluation passes, the averaged generator and FID never see an augmented image."""

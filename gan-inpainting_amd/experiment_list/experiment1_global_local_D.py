@@ -11,6 +11,7 @@ from ..lib import pytorch_ssim
 
 def begin(state, loaders):
     state, exp_dir, logger, device = C.setup(state, "experiment1_global_local_D")
+    C.refuse_lpips_loss(state, "experiment1_global_local_D")
     if state.get("diffaug"):
         raise ValueError("--diffaug is not defined for experiment1_global_local_D: its local critic looks at mask * x (DESIGN.md 4.8)")
     net_G, (net_Dg, net_Dl) = C.build_networks(state, device, n_disc=2, sigmoid=True)

@@ -6,6 +6,7 @@ from . import _common as C
 
 def begin(state, loaders):
     state, exp_dir, logger, device = C.setup(state, "minimaxgan_rmse")
+    C.refuse_lpips_loss(state, "minimaxgan_rmse")
     net_G, (net_D,) = C.build_networks(state, device, n_disc=1, sigmoid=True)
     opt_G, opt_D = C.make_optimizers("adam", net_G, net_D.parameters())
     step = C.trainer.MinimaxStep(net_G, net_D, opt_G, opt_D, recon="rmse", sync=C.make_sync(), diffaug=C.make_diffaug(state))

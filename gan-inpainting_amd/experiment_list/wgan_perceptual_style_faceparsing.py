@@ -38,7 +38,7 @@ def begin(state, loaders):
     pgrad = pgrad and vgg is not None
     step = C.trainer.WGANPerceptualStep(net_G, net_D, opt_G, opt_D, vgg=vgg, segment_model=seg, clip=0.01, sync=C.make_sync(),
                                         overlap=bool(state.get("overlap", True)), perceptual_grad=pgrad,
-                                        diffaug=C.make_diffaug(state))
+                                        diffaug=C.make_diffaug(state), **C.lpips_loss_kw(state))
     step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 

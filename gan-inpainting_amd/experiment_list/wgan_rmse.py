@@ -12,7 +12,7 @@ def begin(state, loaders):
     opt_G, opt_D = C.make_optimizers("rmsprop", net_G, net_D.parameters())
     step = C.trainer.WGANStep(net_G, net_D, opt_G, opt_D, recon="rmse", clip=0.01, sync=C.make_sync(),
                               gp_lambda=float(state.get("gp_lambda", 0.0)), overlap=bool(state.get("overlap", True)),   # > 0: WGAN-GP extension instead of clipping
-                              diffaug=C.make_diffaug(state))
+                              diffaug=C.make_diffaug(state), **C.lpips_loss_kw(state))
     step.ema_G = C.make_ema(state, net_G)
     counters = {"G_iter_count": 0}
 

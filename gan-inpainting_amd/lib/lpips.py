@@ -3,9 +3,14 @@
     m = LPIPS().to(device); m.load_state_dict(torch.load("vgg16.pth") | torch.load("lpips_vgg.pth"))
     d = m.distance(a, b)          # (n,) device tensor = lpips.LPIPS(net='vgg')(a3, b3, normalize=True) of the grey images repeated over 3 channels
 
-A metric of the evaluation pass only (lib/models/evaluate.py: calculate_metric(..., lpips_model=m)): no backward. Grey (n,1,H,W) float32
+    m = LPIPS(grad=True)...;  d, g = m.distance_and_grad(a, b)   # also g[i] = d d[i] / d a[i] (b constant), (n,1,H,W) float32
+
+The metric of the evaluation pass (lib/models/evaluate.py: calculate_metric(..., lpips_model=m)) and, with grad=True, a training term
+(lib/models/loss.py: lpips_loss; csrc/lpips.hip's backward, DESIGN 4.13). grad=True binds a second workspace that keeps the feature maps;
+without it nothing more is allocated or launched than before. Grey (n,1,H,W) float32
 images in [0,1] with H, W multiples of 16; colour inputs are a separate piece of work. No weight file is ever downloaded: the constructor
-initialises like torchvision does for `pretrained=False` (He-normal fan_out, zero bias) with lin = 1/C and the published scaling constants."""
+initialises like torchvision does for `pretrained=False` (He-normal fan_out, zero bias) with lin = 1/C and the published scaling constants,
+and only such stand-in weights have been run here."""
 import ctypes as C
 import re
 
@@ -22,9 +27,10 @@ class LPIPS(nn.Module):
     SHIFT = (-.030, -.088, -.188)
     SCALE = (.458, .448, .450)
 
-    def __init__(self, max_pairs=16):
+    def __init__(self, max_pairs=16, grad=False):
         super().__init__()
         self.max_pairs = int(max_pairs)
+        self.grad = bool(grad)
         sizes, cin = [], 3
         for cout in self.CHANNELS:
             sizes.append((cout, cin))
@@ -111,7 +117,12 @@ class LPIPS(nn.Module):
             ws = torch.empty(lib.gi_lpips_workspace_bytes(hd) + 256, dtype=torch.uint8, device=dev)
             off = (-ws.data_ptr()) % 256
             B.check(lib.gi_lpips_bind(hd, B.ptr(self.flat), ws.data_ptr() + off, ws.numel() - off))
-            self._handles[key] = (hd, ws)
+            gws = None
+            if self.grad:
+                gws = torch.empty(lib.gi_lpips_grad_workspace_bytes(hd) + 256, dtype=torch.uint8, device=dev)
+                goff = (-gws.data_ptr()) % 256
+                B.check(lib.gi_lpips_bind_grad(hd, gws.data_ptr() + goff, gws.numel() - goff))
+            self._handles[key] = (hd, (ws, gws))
             self._dirty = True
         hd = self._handles[key][0]
         if self._dirty:
@@ -152,6 +163,45 @@ class LPIPS(nn.Module):
             if per_layer:
                 layers[:, i:i + k] = part
         return (out, layers) if per_layer else out
+
+    @torch.no_grad()
+    def distance_and_grad(self, a, b, gscale=1.0, per_layer=False):
+        """(d, grad): d as `distance` (the same kernels: the same bits as a grad=False model gives for chunks of the same size), grad
+        (n,1,H,W) float32 with grad[i] = gscale * d d[i] / d a[i]; b is a constant. Chunked by max_pairs; every image carries its own
+        power-of-two scale through the fp16 backward, so its gradient does not depend on what else is in its chunk beyond the kernel
+        dispatch caveat of `distance`. Needs LPIPS(grad=True)."""
+        if not self.grad:
+            raise B.BackendError("LPIPS.distance_and_grad needs LPIPS(grad=True): the backward keeps the feature maps in a second workspace")
+        self._check(a)
+        self._check(b)
+        if a.shape != b.shape:
+            raise ValueError(f"LPIPS.distance_and_grad: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+        a, b = a.detach().contiguous(), b.detach().contiguous()
+        n = a.shape[0]
+        hd = self._handle(a.shape[2], a.shape[3], a.device)
+        out = torch.empty(n, dtype=torch.float32, device=a.device)
+        grad = torch.empty_like(a)
+        layers = torch.empty(5, n, dtype=torch.float32, device=a.device) if per_layer else None
+        for i in range(0, n, self.max_pairs):
+            k = min(self.max_pairs, n - i)
+            part = torch.empty(5, k, dtype=torch.float32, device=a.device) if per_layer else None
+            B.check(B.lib().gi_lpips_distance_grad(hd, B.ptr(a[i:i + k]), B.ptr(b[i:i + k]), k, B.ptr(out[i:i + k]), B.ptr(part),
+                                                   B.ptr(grad[i:i + k]), float(gscale)))
+            if per_layer:
+                layers[:, i:i + k] = part
+        return (out, grad, layers) if per_layer else (out, grad)
+
+    @torch.no_grad()
+    def grad_tap(self, tap, like):
+        """Gradient w.r.t. the post-ReLU map of tap 0..4 of the last distance_and_grad chunk on the handle `like` (its input `a`) ran on,
+        as (n,C,h,w) float32, gscale not applied (parity checks); like.shape[0] <= max_pairs."""
+        if not self.grad:
+            raise B.BackendError("LPIPS.grad_tap needs LPIPS(grad=True)")
+        hd = self._handle(like.shape[2], like.shape[3], like.device)
+        s = 1 << tap
+        out = torch.empty(like.shape[0], self.TAP_CHANNELS[tap], like.shape[2] // s, like.shape[3] // s, dtype=torch.float32, device=like.device)
+        B.check(B.lib().gi_lpips_grad_tap(hd, int(tap), B.ptr(out)))
+        return out
 
     @torch.no_grad()
     def features(self, x, tap):

@@ -202,6 +202,31 @@ def style_loss(output, target, weight=0.1, differentiable=False):
     return _vgg_for(output).perceptual_and_style(output, target, 0.0, weight)[1]
 
 
+class _LpipsFn(torch.autograd.Function):
+    """weight * mean_i d_i with its gradient w.r.t. `output` computed in the forward call (one VGG-16 forward + backward on the device)."""
+
+    @staticmethod
+    def forward(ctx, output, target, model, weight):
+        d, grad = model.distance_and_grad(output, target, gscale=float(weight) / output.shape[0])
+        ctx.grad = grad
+        return d.mean() * float(weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.grad * g, None, None, None
+
+
+def lpips_loss(output, target, model, weight=1.0):
+    """weight * mean_i LPIPS(output[i], target[i]) (lib.lpips.LPIPS; not in the reference). With an `output` that requires grad the scalar
+    carries the analytic gradient w.r.t. `output` (model must be LPIPS(grad=True)); otherwise it is the metric's forward and no gradient
+    is taken. `target` is a constant."""
+    if output.requires_grad:
+        if not getattr(model, "grad", False):
+            raise B.BackendError("lpips_loss on an output that requires grad needs LPIPS(grad=True)")
+        return _LpipsFn.apply(output, target, model, weight)
+    return model.distance(output, target).mean() * float(weight)
+
+
 class _TVFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, tv_weight):

@@ -165,6 +165,12 @@ def build_parser():
                              "package's vgg.pth, or one full LPIPS state dict. The evaluation pass then adds `lpips`, the mean learned "
                              "perceptual distance between composite and ground truth (HIP, lib/lpips.py); every rank evaluates its "
                              "shard. Nothing is ever downloaded; without the flag nothing changes")
+    parser.add_argument("--lpips-loss", dest="lpips_loss", type=float, default=0.0, metavar="W",
+                        help="> 0: add W * mean LPIPS(inpainted, ground) to the generator's loss of the WGAN plugins, with its analytic "
+                             "image gradient (HIP backward of the VGG-16 metric network, DESIGN.md 4.13; not in the reference). Needs "
+                             "--lpips-weights: one model serves the loss and the metric. Not for the minimax plugins and "
+                             "experiment1_global_local_D. Only stand-in weights have been run: the fp16 range of the published weights' "
+                             "activations and gradients is unchecked")
     parser.add_argument("--data", default="synthetic")
     parser.add_argument("--masks", choices=["files", "rect", "freeform"], default="files",
                         help="files: the masks the data supplies (the mask_source files of --data <dir>; host rectangles for "
@@ -220,6 +226,14 @@ def main(argv=None):
         parser.error("--spectral-norm normalises the PatchGAN critic only: it cannot be combined with -d dcgan")
     if args.sn_iterations < 1:
         parser.error("--sn-iterations must be >= 1")
+    if args.lpips_loss < 0:
+        parser.error("--lpips-loss must be >= 0")
+    if args.lpips_loss and not args.lpips_weights:
+        parser.error("--lpips-loss needs --lpips-weights: the term is computed by the metric's network")
+    if args.lpips_loss:
+        refused = [e for e in args.experiments if e.startswith("minimaxgan") or e.startswith("experiment1")]
+        if refused:
+            parser.error(f"--lpips-loss is not defined for {', '.join(refused)}: only the WGAN plugins take the term")
     state = vars(args)
 
     import gan_inpainting_amd  # noqa: F401
@@ -293,7 +307,7 @@ def main(argv=None):
         merged = {}
         for path in args.lpips_weights:
             merged.update(torch.load(path, map_location="cpu"))
-        lpips_model = LPIPS()
+        lpips_model = LPIPS(grad=bool(args.lpips_loss))      # --lpips-loss: the same object also back-propagates
         lpips_model.load_state_dict(merged)
         state["lpips_model"] = lpips_model.to(torch.device("cuda", torch.cuda.current_device()))
     for name in args.experiments:

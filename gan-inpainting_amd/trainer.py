@@ -350,7 +350,11 @@ class _StepBase:
 
 
 class MinimaxStep(_StepBase):
-    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True, ema_G=None, diffaug=None):
+    def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", sync=None, stacked=True, ema_G=None, diffaug=None, lpips=None,
+                 lpips_weight=0.0):
+        if lpips is not None or lpips_weight:
+            raise B.BackendError("MinimaxStep takes no LPIPS term: only the WGAN steps (WGANStep, WGANPerceptualStep) are pinned "
+                                 "against an oracle step with an extra generator loss")
         super().__init__(net_G, [net_D], net_G.device, sync, ema_G, diffaug)
         self.D, self.optG, self.optD, self.recon = net_D, opt_G, opt_D, recon
         self.stacked = stacked      # D(ground) | D(inpainted) as one batch with per-half BatchNorm (see _d_pair)
@@ -396,9 +400,15 @@ class WGANStep(_StepBase):
     package's RMSprop its `clamp` is set so the clip is fused into the optimizer kernel."""
 
     def __init__(self, net_G, net_D, opt_G, opt_D, recon="l1", clip=0.01, sync=None, gp_lambda=0.0, overlap=False, stacked=True,
-                 ema_G=None, diffaug=None):
+                 ema_G=None, diffaug=None, lpips=None, lpips_weight=0.0):
         super().__init__(net_G, [net_D], net_G.device, sync, ema_G, diffaug)
         self.D, self.optG, self.optD, self.recon, self.clip = net_D, opt_G, opt_D, recon, clip
+        # lpips (lib.lpips.LPIPS(grad=True), NOT in the reference): lpips_weight * mean_i LPIPS(inpainted_i, ground_i) joins the
+        # generator's loss with its analytic image gradient (csrc/lpips.hip, DESIGN 4.13). None: nothing is allocated or launched
+        self.lpips, self.lpips_weight = lpips, float(lpips_weight)
+        if lpips is not None and not getattr(lpips, "grad", False):
+            raise B.BackendError("WGANStep(lpips=...) needs lib.lpips.LPIPS(grad=True)")
+        self._lpips_fold, self._lpips_scaled_for = 0.0, None
         # stacked=True: the critic's two calls of a batch, D(ground) and D(inpainted) (wgan_l1.py:134-135), run as ONE
         # 2n batch with independent BatchNorm statistics per half (gi_net_set_bn_groups): same arithmetic per
         # image, half the launches, and one weight-gradient GEMM over both halves instead of two accumulating ones.
@@ -500,7 +510,7 @@ class WGANStep(_StepBase):
             # before the wait - the main stream has nothing else to do while the critic runs: clearing the generator's gradients
             # and every loss term that depends on (inpainted, ground) only, i.e. all but the adversarial one
             self.optG.zero_grad()
-            g_other = self._g_losses(inp, ground)
+            g_other = self._g_terms(inp, ground)
             main.wait_event(self._evD[k])
             d_adv.record_stream(main)
             o.add(d_adv, g_other, self.tmp1)
@@ -555,12 +565,50 @@ class WGANStep(_StepBase):
         if update_g:                                                            # cadence :157-163 is the caller's
             self.optG.zero_grad()
             d_adv = self._d_for_g(self.D, self.inpainted, MEAN, 0.0, "g_adv", +1.0)
-            o.add(d_adv, self._g_losses(self.inpainted, ground), self.tmp1)
+            o.add(d_adv, self._g_terms(self.inpainted, ground), self.tmp1)
             o.mul(self.tmp1, self.mask_c, self.g_gen)
             self._bwd_G(gtok, self.g_gen)
             self._step_G(self.optG)
         self._aug_step += 1
         return self.L
+
+    def _g_terms(self, inp, ground):
+        """_g_losses plus, with lpips set, the LPIPS term: records L["lpips_loss"], adds its image gradient to the other terms'
+        (before the mask multiply of the caller)."""
+        if self.lpips is None:
+            return self._g_losses(inp, ground)
+        refold = self.auto_loss_scale and self.G._dtype == B.GI_F16 and self._lpips_scaled_for != self._shape
+        if refold:
+            self.recon_weight -= self._lpips_fold
+            self._lpips_fold = 0.0
+        g = self._g_losses(inp, ground)
+        n, _, h, w = inp.shape
+        d, gl = self.lpips.distance_and_grad(inp, ground, gscale=self.lpips_weight / n)
+        self.L["lpips_loss"] = (d.sum() * (self.lpips_weight / n)).view(1)
+        if refold:
+            # as WGANPerceptualStep does for its VGG-19 terms (DESIGN 4.5): the fp16 generator's loss scale assumes
+            # ~ recon_weight / (N H W) per pixel; ONE host read at the first generator update of a batch geometry puts this term's
+            # largest per-pixel gradient, in the same units, on top
+            self._lpips_fold = float(gl.abs().max()) * n * h * w
+            self.recon_weight += self._lpips_fold
+            self._pick_loss_scales(ground)
+            self._lpips_scaled_for = self._shape
+        self.ops.add(g, gl, g)
+        return g
+
+    def _extra_state(self):
+        st = super()._extra_state()
+        if self.lpips is not None:
+            st = dict(st, recon_weight=float(self.recon_weight), lpips_fold=float(self._lpips_fold),
+                      lpips_scaled_for=None if self._lpips_scaled_for is None else list(self._lpips_scaled_for))
+        return st
+
+    def _load_extra_state(self, d):
+        super()._load_extra_state(d)
+        if self.lpips is not None and "lpips_fold" in d:
+            self.recon_weight = float(d["recon_weight"])
+            self._lpips_fold = float(d["lpips_fold"])
+            self._lpips_scaled_for = None if d.get("lpips_scaled_for") is None else tuple(d["lpips_scaled_for"])
 
     def _critic_stacked(self, ground, inp, x2=None, real_done=False):
         """D(ground) and D(inpainted) of wgan_l1.py:134-141 as one [ground | inpainted] batch, BatchNorm per half;
@@ -671,7 +719,11 @@ class DualDStep(_StepBase):
     """G step first, LSGAN losses, global + local (mask * x) discriminators, mask not ceil-ed,
     output not composited, one optimizer over both discriminators (:123)."""
 
-    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True, ema_G=None, diffaug=None):
+    def __init__(self, net_G, net_Dg, net_Dl, opt_G, opt_D, lam1=300.0, lam2=300.0, sync=None, stacked=True, ema_G=None, diffaug=None,
+                 lpips=None, lpips_weight=0.0):
+        if lpips is not None or lpips_weight:
+            raise B.BackendError("DualDStep takes no LPIPS term: only the WGAN steps (WGANStep, WGANPerceptualStep) are pinned "
+                                 "against an oracle step with an extra generator loss")
         if diffaug is not None:
             # the local critic looks at mask * x: whether it shares the global critic's transform is undecided (DESIGN 4.8)
             raise B.BackendError("DualDStep does not support diffaug")

@@ -420,7 +420,8 @@ int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* 
 int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw_f32);
 
 /* LPIPS (Zhang et al. 2018; `lpips` v0.1 with net = 'vgg', normalize = True, spatial = False) between grey images repeated
- * over 3 channels: VGG-16 taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3, each before its max pool. Forward only (a metric).
+ * over 3 channels: VGG-16 taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3, each before its max pool. The entries of this block are
+ * the forward (the metric); the opt-in backward follows below.
  * H, W: multiples of 16, >= 16; 2 * max_pairs * H * W * 64 < 2^31. params (fp32, gi_lpips_tensor_desc gives name, shape, offset):
  * the 13 convolutions "features.<i>.weight|bias" (torchvision vgg16 indices 0,2,5,7,10,12,14,17,19,21,24,26,28), the five
  * "lin<k>.model.1.weight" vectors (64,128,256,512,512), "scaling_layer.shift" and "scaling_layer.scale" (3 each). The scaling
@@ -443,6 +444,21 @@ int gi_lpips_bind(gi_lpips* v, const float* params, void* ws, int64_t ws_bytes);
 int gi_lpips_sync_weights(gi_lpips* v);                                            /* after params change */
 int gi_lpips_distance(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n);
 int gi_lpips_features(gi_lpips* v, const float* x, int n, int tap, float* out_nchw);
+/* Opt-in backward of the distance w.r.t. `a` (b is a constant). It keeps the forward's feature maps in a separate workspace: query,
+ * bind after gi_lpips_bind (256-byte aligned), then gi_lpips_sync_weights. A handle that never binds it reports the same
+ * gi_lpips_workspace_bytes and runs exactly as without these entries; every entry below fails with GI_ERR_INVALID on such a handle.
+ * gi_lpips_distance_grad: out_n / per_layer_5n as gi_lpips_distance (same kernels, same bits); grad_a: n*H*W floats,
+ * grad_a[i] = gscale * d out_n[i] / d a[i]. fp16 with fp32 accumulation at one power-of-two scale PER IMAGE, chosen on the device
+ * from the image's largest seed and removed in fp32 by the last kernel; bit-reproducible (no float atomics); a[i] == b[i] gives an
+ * exactly zero gradient. A pixel whose tap vector of `a` is all zero contributes no seed (autograd's 0 * inf there is NaN): the ReLU
+ * mask below removes every channel of such a vector anyway.
+ * gi_lpips_grad_tap (parity / debugging): the gradient w.r.t. the post-ReLU map of tap 0..4 of the last grad call as (n,C,h,w)
+ * fp32, gscale not applied; replays that call's backward from the workspace. */
+int64_t gi_lpips_grad_workspace_bytes(const gi_lpips* v);
+int gi_lpips_bind_grad(gi_lpips* v, void* ws, int64_t ws_bytes);
+int gi_lpips_distance_grad(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n, float* grad_a,
+                           float gscale);
+int gi_lpips_grad_tap(gi_lpips* v, int tap, float* out_nchw_f32);
 
 /* ---- Frechet Inception Distance (reference lib/fid/): Inception-V3 pool3 features + streaming statistics ----
  * The FID variant of Inception-V3 (lib/fid/inception.py: average pools that do not count padding in Mixed_5b..5d,
@@ -939,6 +955,21 @@ int gi_debug_lpips_fold(gi_ctx* ctx, const float* w, const float* shift, const f
 int64_t gi_debug_lpips_tap_ws_bytes(int n);
 int gi_debug_lpips_tap(gi_ctx* ctx, const void* F, int n, int H, int W, int C, const float* lin, void* ws, int64_t ws_bytes,
                        float* d_n, void* pooled);
+/* the LPIPS backward's kernels (restated by tests/lpips_grad_ref.py).
+ * pack_t: w [cout][cin][3][3] fp32 -> fp16 [cin][8 - tap][cout], the weights of the transposed convolution.
+ * seed: F [2n][HW][C] fp16 (a images, then b images), lin [C]. store = 0: smax[i] = max(smax[i], max |seed of pair i|) as a bit
+ * pattern; store = 1: sc[i] * seed in fp16 over the b half of F. seed = d d_l / d a (see gi_lpips_distance_grad), 0 where a is 0.
+ * scale: sc[i] = s_i, the power of two that puts smax[i] into [2^-3, 2^-2) (1 when smax[i] is 0), sc[n + i] = 1 / s_i.
+ * act_bwd: pool = 0: out = [act > 0 or !relu] * (g + seed), g / seed may be NULL, out may be g. pool = 1: g (n,H/2,W/2,C) routed to
+ * the first maximum of every 2x2 window of act (n,H,W,C), then out = [act > 0 or !relu] * (routed g + seed) (seed may be NULL).
+ * conv1_adjoint: dimg (n,H,W fp32) = gscale * sc_inv[i] * adjoint of the 1 -> 64 convolution wA [64][9] applied to D (n,H,W,64) fp16. */
+int gi_debug_lpips_pack_t(gi_ctx* ctx, const float* w, void* out, int cout, int cin);
+int gi_debug_lpips_seed(gi_ctx* ctx, int store, void* F, int n, int HW, int C, const float* lin, unsigned* smax, const float* sc);
+int gi_debug_lpips_scale(gi_ctx* ctx, const unsigned* smax, float* sc, int n);
+int gi_debug_lpips_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W,
+                           int C, int relu);
+int gi_debug_lpips_conv1_adjoint(gi_ctx* ctx, const void* D, const float* wA, const float* sc_inv, float gscale, float* dimg, int n,
+                                 int H, int W);
 /* fp32 master [a][16][b] -> T [a][16*b] (w_packed) and T [4][b][4*a] (w_phase); either may be NULL */
 int gi_pack_weights(gi_ctx* ctx, int dtype, const float* w, int ca, int cb, void* w_packed, void* w_phase);
 int gi_convert(gi_ctx* ctx, int dtype, const float* src, void* dst, int64_t count);      /* fp32 -> T */
