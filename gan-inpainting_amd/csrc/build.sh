@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=${GI_OUT:-../libganinpaint.so}      # GI_OUT / GI_BUILD_DIR: a second build beside the shipped one (tools: ablation A/B, -DGI_ABLATION)
 BUILD=${GI_BUILD_DIR:-build}
-SRCS="api.hip igemm_plan.hip igemm.hip igemm3.hip igemm5.hip igemm7.hip igemm8.hip wgrad.hip wgrad2.hip c1.hip head.hip elementwise.hip norm.hip ssim.hip evalmetrics.hip auxloss.hip vgg.hip resize.hip maskgen.hip batchgather.hip imageout.hip components.hip diffaug.hip comm.hip net.hip specnorm.hip dcgan.hip inception.hip featmetrics.hip lpips.hip"
+SRCS="api.hip igemm_plan.hip igemm.hip igemm3.hip igemm5.hip igemm7.hip igemm8.hip wgrad.hip wgrad2.hip c1.hip head.hip elementwise.hip norm.hip ssim.hip evalmetrics.hip auxloss.hip vggtrunk.hip vgg.hip resize.hip maskgen.hip batchgather.hip imageout.hip components.hip diffaug.hip comm.hip net.hip specnorm.hip dcgan.hip inception.hip featmetrics.hip lpips.hip"
 OBJS=""
 mkdir -p $BUILD
 pids=""

@@ -2,7 +2,8 @@
 // inpainting papers report next to FID. The evaluation pass uses the forward alone; the opt-in backward w.r.t. `a` (second
 // half of this file) needs a second workspace, and a handle that never binds it runs launch for launch as without it.
 //
-// `a` and `b` run as ONE stacked batch of 2n images (NHWC fp16), as in vgg.hip:
+// `a` and `b` run as ONE stacked batch of 2n images (NHWC fp16), as in vgg.hip; what the two networks' trunks share (weight packing,
+// read-backs, and the backward's scale, activation backward, first-layer adjoint, workspace arenas and chain) is vggtrunk.hip's:
 //   conv1_1  the network's input is alpha_c x + beta_c per channel (the scaling layer after normalize=True) of the grey image repeated
 //            over 3 channels, ZERO-PADDED AFTER the scaling: the beta term is a bias that is missing where a tap falls outside the image,
 //            so it differs on the one-pixel border ring (nine position classes) and cannot go into the layer's bias. The layer is a
@@ -15,7 +16,7 @@
 //            maps instead of two). No atomics: an image's value has the same bits wherever it sits in the batch and whatever n is.
 #include <new>
 
-#include "common.h"
+#include "vggtrunk.h"
 
 namespace {
 
@@ -23,20 +24,10 @@ constexpr int NCONV = 13, NTAP = 5;
 const int kCin[NCONV] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
 const int kCout[NCONV] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
 const int kFeatIdx[NCONV] = {0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28};   // torchvision vgg16.features indices
-const int kTapAfter[NCONV] = {-1, 0, -1, 1, -1, -1, 2, -1, -1, 3, -1, -1, 4};   // a 2x2 max pool follows every tap but the last
+const int kTapAfter[NCONV] = {-1, 0, -1, 1, -1, -1, 2, -1, -1, 3, -1, -1, 4};
+const int kPoolAfter[NCONV] = {0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 0};          // a 2x2 max pool follows every tap but the last
 const int kTapC[NTAP] = {64, 128, 256, 512, 512};
 constexpr int LP_MAXNB = 128;      // workgroups (= fp64 partials) per image and tap, at most
-
-// [cout][cin][3][3] fp32 -> fp16 [cout][tap][cin] (what the mode-2 kernels read; vgg.hip's pack3x3_kernel)
-__global__ void __launch_bounds__(256) lpips_pack3x3_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
-  const int64_t total = (int64_t)cout * 9 * cin;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c = (int)(i % cin);
-    const int t = (int)((i / cin) % 9);
-    const int o = (int)(i / ((int64_t)cin * 9));
-    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + t];
-  }
-}
 
 // wA[o][tap] = sum_c w[o][c][tap] * alpha_c, wB[o][tap] = sum_c w[o][c][tap] * beta_c with alpha_c = 2 / scale_c and
 // beta_c = (-1 - shift_c) / scale_c: (2 x - 1 - shift_c) / scale_c = alpha_c x + beta_c. fp32, c ascending, one fma per term.
@@ -231,26 +222,6 @@ __global__ void __launch_bounds__(256) lpips_tap_kernel(LpTapP p) {
   if (threadIdx.x == 0) p.partial[(int64_t)img * LP_MAXNB + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-#ifdef GI_LPIPS_UNFUSED
-// the separate pooling pass of the A/B build (tools/time_lpips.py): NHWC fp16 2x2 / stride 2 max pooling, 8 channels per thread
-__global__ void __launch_bounds__(256) lpips_maxpool2_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int nimg, int Ho, int Wo, int C) {
-  const int cg = C / 8;
-  const int64_t total = (int64_t)nimg * Ho * Wo * cg;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int g = (int)(i % cg);
-    const int64_t px = i / cg;
-    const int x = (int)(px % Wo);
-    const int64_t t = px / Wo;
-    const int y = (int)(t % Ho);
-    const int64_t img = t / Ho;
-    const half_t* s = in + (((img * 2 * Ho + 2 * y) * 2 * Wo + 2 * x) * (int64_t)C) + g * 8;
-    const h8_t a = *(const h8_t*)s, b = *(const h8_t*)(s + C);
-    const h8_t c = *(const h8_t*)(s + (int64_t)2 * Wo * C), d = *(const h8_t*)(s + (int64_t)2 * Wo * C + C);
-    *(h8_t*)(out + px * C + g * 8) = __builtin_elementwise_max(__builtin_elementwise_max(a, b), __builtin_elementwise_max(c, d));
-  }
-}
-#endif
-
 // Workgroup i: d_l[i] = inv[l] * (the nb[l] partials of pair i and tap l, added in a fixed order), rounded to fp32; out_n[i] = their sum
 // (fp64, l ascending, rounded once). per_layer[l * n + i] = d_l[i] when given.
 struct LpFinP { int nb[NTAP]; double inv[NTAP]; int ntap, n, pair_stride; };
@@ -274,37 +245,12 @@ __global__ void __launch_bounds__(256) lpips_finish_kernel(const double* __restr
   if (out_n && threadIdx.x == 0) out_n[i] = (float)tot;
 }
 
-// NHWC fp16 feature map -> NCHW fp32 (parity / debugging)
-__global__ void __launch_bounds__(256) lpips_nhwc_to_nchw_kernel(const half_t* __restrict__ in, float* __restrict__ out, int nimg, int HW, int C) {
-  const int64_t total = (int64_t)nimg * HW * C;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int px = (int)(i % HW);
-    const int64_t t = i / HW;
-    const int c = (int)(t % C);
-    const int64_t img = t / C;
-    out[i] = (float)in[(img * HW + px) * C + c];
-  }
-}
-
 // ================================================================================================================================
 // Opt-in backward: gscale * d d[i] / d a[i], b constant. As vgg.hip's the chain runs on s * gradient in fp16
 // with fp32 accumulation, but with ONE power of two s_i PER IMAGE: d[i] depends on a[i] alone and every kernel of the chain is linear
 // per image, so a nearly identical pair does not underflow next to a very different one and an image's bits do not depend on its
 // chunk-mates. No float atomics: the only atomic is an unsigned max over bit patterns of non-negative floats (order-independent).
 // ================================================================================================================================
-
-// [cout][cin][3][3] fp32 -> fp16 [cin][tap'][cout], tap' = 8 - tap: the transpose of a 3x3 / s1 / p1 convolution is that convolution with
-// the taps reversed and the channel roles exchanged, so the input-gradient GEMMs run on the forward's mode-2 kernels (vgg.hip's
-// pack3x3_t_kernel)
-__global__ void __launch_bounds__(256) lpips_pack3x3_t_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
-  const int64_t total = (int64_t)cin * 9 * cout;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int o = (int)(i % cout);
-    const int t = (int)((i / cout) % 9);
-    const int c = (int)(i / ((int64_t)cout * 9));
-    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + (8 - t)];
-  }
-}
 
 // Seed of one pixel: the gradient of d_l w.r.t. the post-ReLU vector a (b constant), in the tap kernel's lane layout. With ra = |a|,
 // ia = 1 / (ra + 1e-10), a^ = a ia, delta = a^ - b^ (the forward's rounded products: equal inputs give delta = 0 exactly) and
@@ -390,150 +336,8 @@ __global__ void __launch_bounds__(256) lpips_seed_kernel(LpSeedP p) {
   }
 }
 
-// Image i: s_i = 2^(kLpSeedExp - e) with its largest seed over the five taps m 2^e, m in [0.5, 1): the largest scaled seed lands in
-// [2^(kLpSeedExp - 1), 2^kLpSeedExp). All seeds zero (a[i] == b[i]) or a non-finite maximum: s_i = 1. sc[i] = s_i, sc[n + i] = 1 / s_i.
-// kLpSeedExp = -2: headroom as derived in DESIGN 4.13.
-constexpr int kLpSeedExp = -2;
-__global__ void __launch_bounds__(64) lpips_scale_kernel(const unsigned* __restrict__ smax, float* __restrict__ sc, int n) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  const float am = __uint_as_float(smax[i]);
-  int ex = 0;
-  float s = 1.f;
-  if (am > 0.f && am < INFINITY) {
-    (void)frexpf(am, &ex);
-    int k = kLpSeedExp - ex;
-    k = k > 100 ? 100 : (k < -100 ? -100 : k);
-    s = ldexpf(1.f, k);
-  }
-  sc[i] = s;
-  sc[n + i] = 1.f / s;
-}
-
-// Activation backward between two input-gradient GEMMs, 16-byte NHWC accesses, 8 channels per thread; one fp16 rounding of the fp32 sum:
-//   POOL = false: out = [act > 0] * (g + seed)                        (g and / or seed may be null; out may alias g)
-//   POOL = true:  g lives on the (H/2, W/2) grid: every 2x2 window of `act` routes its value to the first maximum in row-major order
-//                 (F.max_pool2d's backward; the arg-max is recomputed from the kept map), then out = [act > 0] * (routed g + seed) at all
-//                 four positions (seed may be null). The taps of this network are the pooled layers, so the seed joins here.
-// relu = 0 drops the [act > 0] factor: the gradient w.r.t. the post-ReLU map itself (gi_lpips_grad_tap).
-template <bool POOL>
-__global__ void __launch_bounds__(256) lpips_act_bwd_kernel(const half_t* g, const half_t* __restrict__ act, const half_t* __restrict__ seed,
-                                                            half_t* out, int nimg, int H, int W, int C, int relu) {
-  const int cg = C / 8;
-  const h8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  if constexpr (!POOL) {
-    const int64_t total = (int64_t)nimg * H * W * cg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-      const h8_t a = *(const h8_t*)(act + i * 8);
-      const h8_t gv = g ? *(const h8_t*)(g + i * 8) : z8;
-      const h8_t sv = seed ? *(const h8_t*)(seed + i * 8) : z8;
-      h8_t o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (!relu || (float)a[e] > 0.f) ? (half_t)((float)gv[e] + (float)sv[e]) : (half_t)0.f;
-      *(h8_t*)(out + i * 8) = o;
-    }
-  } else {
-    const int Ho = H / 2, Wo = W / 2;
-    const int64_t total = (int64_t)nimg * Ho * Wo * cg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-      const int gq = (int)(i % cg);
-      const int64_t pq = i / cg;
-      const int x = (int)(pq % Wo);
-      const int64_t tt = pq / Wo;
-      const int y = (int)(tt % Ho);
-      const int64_t img = tt / Ho;
-      const int64_t o00 = (((img * H + 2 * y) * W + 2 * x) * (int64_t)C) + gq * 8;
-      const int64_t off[4] = {o00, o00 + C, o00 + (int64_t)W * C, o00 + (int64_t)W * C + C};
-      h8_t a[4], sv[4], o[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { a[q] = *(const h8_t*)(act + off[q]); sv[q] = seed ? *(const h8_t*)(seed + off[q]) : z8; }
-      const h8_t gv = *(const h8_t*)(g + pq * C + gq * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        int best = 0;
-        float bv = (float)a[0][e];
-#pragma unroll
-        for (int q = 1; q < 4; ++q) { const float av = (float)a[q][e]; if (av > bv) { bv = av; best = q; } }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float val = (q == best ? (float)gv[e] : 0.f) + (float)sv[q][e];
-          o[q][e] = (!relu || (float)a[q][e] > 0.f) ? (half_t)val : (half_t)0.f;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(h8_t*)(out + off[q]) = o[q];
-    }
-  }
-}
-
-// First-layer adjoint: dimg[i][y][x] = mul_i * sum_{ky,kx,o} wA[o][ky][kx] * D[i][y+1-ky][x+1-kx][o] in fp32, wA the folded image-plane
-// weights (the indicator plane is constant and contributes nothing), mul_i = gscale / s_i from device memory: the fp16 scale leaves
-// here. vgg_conv1_adjoint_kernel's tiling: a workgroup owns 16 x 32 pixels, reduces the 64 channels of each of the 18 x 34 halo pixels
-// of D to nine per-tap sums in LDS (one pass over D in 16-byte loads), then every output pixel adds its nine neighbours' sums.
-__global__ void __launch_bounds__(256) lpips_conv1_adjoint_kernel(const half_t* __restrict__ D, const float* __restrict__ wA, const float* __restrict__ sc_inv,
-                                                                  float gscale, float* __restrict__ dimg, int H, int W) {
-  constexpr int TH = 16, TW = 32, HH = TH + 2, HW_ = TW + 2, NH = HH * HW_;
-  __shared__ float T[NH * 9];
-  const int img = blockIdx.z, y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
-  const half_t* Di = D + (int64_t)img * H * W * 64;
-  for (int h = threadIdx.x; h < NH; h += 256) {
-    const int hy = h / HW_, hx = h - hy * HW_;
-    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-    float t[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t[k] = 0.f;
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      const half_t* src = Di + ((int64_t)y * W + x) * 64;
-      h8_t v[8];
-#pragma unroll
-      for (int c8 = 0; c8 < 8; ++c8) v[c8] = *(const h8_t*)(src + c8 * 8);
-#pragma unroll
-      for (int c8 = 0; c8 < 8; ++c8)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = (float)v[c8][e];
-#pragma unroll
-          for (int k = 0; k < 9; ++k) t[k] = fmaf(wA[(c8 * 8 + e) * 9 + k], d, t[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) T[h * 9 + k] = t[k];
-  }
-  __syncthreads();
-  const float mul = gscale * sc_inv[img];
-  for (int o = threadIdx.x; o < TH * TW; o += 256) {
-    const int ty = o / TW, tx = o - ty * TW;
-    const int y = y0 + ty, x = x0 + tx;
-    if (y >= H || x >= W) continue;
-    float s = 0.f;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) s += T[((ty + 2 - ky) * HW_ + (tx + 2 - kx)) * 9 + ky * 3 + kx];
-    dimg[((int64_t)img * H + y) * W + x] = s * mul;
-  }
-}
-
-// NHWC fp16 (s_i * gradient) -> NCHW fp32 gradient (gi_lpips_grad_tap)
-__global__ void __launch_bounds__(256) lpips_nhwc_to_nchw_unscale_kernel(const half_t* __restrict__ in, const float* __restrict__ sc_inv,
-                                                                         float* __restrict__ out, int nimg, int HW, int C) {
-  const int64_t total = (int64_t)nimg * HW * C;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int px = (int)(i % HW);
-    const int64_t t = i / HW;
-    const int c = (int)(t % C);
-    const int64_t img = t / C;
-    out[i] = (float)in[(img * HW + px) * C + c] * sc_inv[img];
-  }
-}
-
 // ---- host launch code: one copy of every grid rule, shared by the runner and the gi_debug_lpips_* entries -----------------------------
 
-int lp_pack3x3(hipStream_t st, const float* w, half_t* out, int cout, int cin) {
-  hipLaunchKernelGGL(lpips_pack3x3_kernel, dim3(grid_for((int64_t)cout * 9 * cin, 256, 2048)), dim3(256), 0, st, w, out, cout, cin);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
 int lp_fold(hipStream_t st, const float* w, const float* shift, const float* scale, float* wA, float* wB) {
   hipLaunchKernelGGL(lpips_fold_kernel, dim3(3), dim3(256), 0, st, w, shift, scale, wA, wB);
   GI_LAUNCH_CHECK();
@@ -545,18 +349,6 @@ int lp_conv1(hipStream_t st, const float* xa, const float* xb, int n, int H, int
                      bias, out);
   GI_LAUNCH_CHECK();
   return GI_OK;
-}
-int lp_conv3x3(hipStream_t st, const half_t* in, const half_t* w, half_t* out, int nimg, int H, int W, int cin, int cout, const float* bias) {
-  IgemmArgs a = IgemmArgs{};
-  a.in = in; a.w = w; a.out = out;
-  a.bias = bias; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
-  a.n = nimg; a.Hs = H; a.Ws = W;
-  a.cin = cin; a.ldin = cin; a.coffin = 0;
-  a.cout = cout; a.ldout = cout; a.coffout = 0;
-  a.relu_in = 0; a.relu_cend = 0; a.act_out = GI_ACT_RELU; a.force_splitk = 0;
-  const int rc = op_igemm(st, GI_F16, 2, a);
-  if (rc == GI_ERR_UNSUPPORTED) gi_set_error("lpips: no mode-2 kernel serves n=%d %dx%d %d->%d", nimg, H, W, cin, cout);
-  return rc;
 }
 // workgroups per image of a tap: a function of the map alone
 int lp_tap_blocks(int H, int W, int C, bool pool) {
@@ -591,11 +383,6 @@ int lp_finish(hipStream_t st, const double* partial, const LpFinP& f, float* out
 }
 
 // ---- the backward's launch code ------------------------------------------------------------------------------------------------------
-int lp_pack3x3_t(hipStream_t st, const float* w, half_t* out, int cout, int cin) {
-  hipLaunchKernelGGL(lpips_pack3x3_t_kernel, dim3(grid_for((int64_t)cout * 9 * cin, 256, 2048)), dim3(256), 0, st, w, out, cout, cin);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
 // one pass of a tap's seed over n pairs (F [2n][HW][C]): store = false: smax[i] = max |seed| of pair i; store = true: sc[i] * seed over the b half
 int lp_seed(hipStream_t st, bool store, half_t* F, int n, int64_t HW, int C, const float* lin, unsigned* smax, const float* sc) {
   LpSeedP p;
@@ -617,49 +404,12 @@ int lp_seed(hipStream_t st, bool store, half_t* F, int n, int64_t HW, int C, con
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
-int lp_scale(hipStream_t st, const unsigned* smax, float* sc, int n) {
-  hipLaunchKernelGGL(lpips_scale_kernel, dim3((n + 63) / 64), dim3(64), 0, st, smax, sc, n);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-int lp_act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
-  if (pool) {
-    hipLaunchKernelGGL(lpips_act_bwd_kernel<true>, dim3(grid_for((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out,
-                       n, H, W, C, relu);
-  } else {
-    hipLaunchKernelGGL(lpips_act_bwd_kernel<false>, dim3(grid_for((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C,
-                       relu);
-  }
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-int lp_conv1_adjoint(hipStream_t st, const half_t* D, const float* wA, const float* sc_inv, float gscale, float* dimg, int n, int H, int W) {
-  hipLaunchKernelGGL(lpips_conv1_adjoint_kernel, dim3((W + 31) / 32, (H + 15) / 16, n), dim3(256), 0, st, D, wA, sc_inv, gscale, dimg, H, W);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-// one input-gradient GEMM: the transposed 3x3 convolution (weights from lp_pack3x3_t) of n gradient maps, no bias, no activation; mask:
-// the ReLU mask of the result's layer in the epilogue, where the dispatched kernel has one (applied: whether it had)
-int lp_conv3x3_bwd(hipStream_t st, const half_t* in, const half_t* wT, half_t* out, int n, int H, int W, int cin, int cout, const half_t* mask, int* applied) {
-  IgemmArgs a = IgemmArgs{};
-  a.in = in; a.w = wT; a.out = out;
-  a.bias = nullptr; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
-  a.n = n; a.Hs = H; a.Ws = W;
-  a.cin = cin; a.ldin = cin; a.coffin = 0;
-  a.cout = cout; a.ldout = cout; a.coffout = 0;
-  a.relu_in = 0; a.relu_cend = 0; a.act_out = GI_ACT_NONE; a.force_splitk = 0;
-  if (mask) { a.mask = mask; a.ldmask = cout; a.coffmask = 0; a.mask_slope = 0.f; a.add = nullptr; a.ldadd = cout; a.coffadd = 0; }
-  const int rc = op_igemm(st, GI_F16, 2, a);
-  if (rc == GI_ERR_UNSUPPORTED) gi_set_error("lpips backward: no mode-2 kernel serves n=%d %dx%d %d->%d", n, H, W, cin, cout);
-  *applied = mask && a.mask_applied;
-  return rc;
-}
 
 }  // namespace
 
 struct gi_lpips {
   gi_ctx* ctx;
-  int H, W, max_pairs;
+  VggTrunk t;             // H, W, max_pairs; w1: conv1_1 folded weights [64][9], image plane (wA); the rest only with the grad workspace
   int64_t woff[NCONV], boff[NCONV], linoff[NTAP], shiftoff, scaleoff;   // float offsets into params
   int64_t param_floats;
   const float* params;
@@ -667,8 +417,7 @@ struct gi_lpips {
   int64_t ws_bytes;
   half_t* act[2];
   half_t* wpk[NCONV];     // [1..12] packed fp16 weights
-  float* wA;              // conv1_1 folded weights [64][9]: image plane
-  float* wB;              //                                 indicator plane
+  float* wB;              // conv1_1 folded weights [64][9]: indicator plane
   double* partial;        // [5 taps][max_pairs][LP_MAXNB]
   bool bound, synced;
   // opt-in backward (gi_lpips_bind_grad): a separate workspace; a handle that never binds it runs exactly as before
@@ -676,70 +425,33 @@ struct gi_lpips {
   int64_t gws_bytes;
   bool gbound;
   int grad_n;             // pairs of the last grad call (0: none yet): gi_lpips_grad_tap replays its backward
-  half_t* ga[NCONV];      // post-ReLU maps, [a half | b half]; the b half survives only at the taps (where the seeds replace it)
-  half_t* gpool[NCONV];   // 2x2 max pool after the four pooled taps (both halves): the next layer's input
-  half_t* wT[NCONV];      // [1..12] fp16 weights of the transposed convolutions: [cin][reversed tap][cout]
-  half_t* gbuf[2];        // gradient ping-pong (n images)
   unsigned* smax;         // [max_pairs] largest |seed| of an image over the five taps (bit patterns of non-negative floats)
-  float* sc;              // [i] = s_i = 2^k, [n + i] = 1 / s_i: image i's backward runs on s_i * gradient
+  float* sc;              // [i] = s_i = 2^k, [n + i] = 1 / s_i (t.inv, stride 1): image i's backward runs on s_i * gradient
 };
 
 namespace {
 
 int64_t lpips_ws_layout(gi_lpips* v, char* base) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
-  const int64_t act_bytes = (int64_t)2 * v->max_pairs * v->H * v->W * 64 * 2;      // the widest maps: relu1_1 / relu1_2
+  WsTake take{base, 0};
+  const int64_t act_bytes = (int64_t)2 * v->t.max_pairs * v->t.H * v->t.W * 64 * 2;      // the widest maps: relu1_1 / relu1_2
   v->act[0] = (half_t*)take(act_bytes);
   v->act[1] = (half_t*)take(act_bytes);
   v->wpk[0] = nullptr;
   for (int i = 1; i < NCONV; ++i) v->wpk[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
-  v->wA = (float*)take(64 * 9 * 4);
+  v->t.w1 = (float*)take(64 * 9 * 4);
   v->wB = (float*)take(64 * 9 * 4);
-  v->partial = (double*)take((int64_t)NTAP * v->max_pairs * LP_MAXNB * 8);
-  return off;
+  v->partial = (double*)take((int64_t)NTAP * v->t.max_pairs * LP_MAXNB * 8);
+  return take.off;
 }
 
-// grad workspace (vgg.hip's arena scheme). The forward's maps go to two arenas, alternating per stage (convolution or pooled tap): a stage
-// reads the other arena and writes [a half | b half] behind what its arena must keep - the a halves of the 13 convolutions (ReLU masks,
-// pool routing) and both halves at the five taps - so a b half nobody needs is overwritten by the stage after next.
+// grad workspace: the trunk's arenas, transposed weights and gradient buffers (the [a half | b half] maps of trunk_gws_layout), then the
+// per-image seed maxima and scales
 int64_t lpips_gws_layout(gi_lpips* v, char* base) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
-  int64_t pos[2] = {0, 0}, ext[2] = {0, 0}, start[2 * NCONV];
-  int H = v->H, W = v->W, k = 0;
-  for (int i = 0; i < NCONV; ++i) {
-    const int64_t half = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
-    start[2 * i] = pos[k & 1];
-    if (start[2 * i] + 2 * half > ext[k & 1]) ext[k & 1] = start[2 * i] + 2 * half;
-    pos[k & 1] += half * (kTapAfter[i] >= 0 ? 2 : 1);
-    ++k;
-    start[2 * i + 1] = -1;
-    if (kTapAfter[i] >= 0 && kTapAfter[i] < NTAP - 1) {
-      H /= 2; W /= 2;
-      start[2 * i + 1] = pos[k & 1];       // kept by nobody: the next stage of this arena starts at the same place
-      const int64_t ph = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
-      if (start[2 * i + 1] + 2 * ph > ext[k & 1]) ext[k & 1] = start[2 * i + 1] + 2 * ph;
-      ++k;
-    }
-  }
-  char* arena[2];
-  arena[0] = take(ext[0]);
-  arena[1] = take(ext[1]);
-  for (int i = 0, kk = 0; i < NCONV; ++i) {
-    v->ga[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i]) : nullptr;
-    ++kk;
-    v->gpool[i] = nullptr;
-    if (start[2 * i + 1] >= 0) { v->gpool[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i + 1]) : nullptr; ++kk; }
-  }
-  v->wT[0] = nullptr;
-  for (int i = 1; i < NCONV; ++i) v->wT[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
-  const int64_t gbytes = (int64_t)v->max_pairs * v->H * v->W * 64 * 2;
-  v->gbuf[0] = (half_t*)take(gbytes);
-  v->gbuf[1] = (half_t*)take(gbytes);
-  v->smax = (unsigned*)take((int64_t)v->max_pairs * 4);
-  v->sc = (float*)take((int64_t)2 * v->max_pairs * 4);
-  return off;
+  WsTake take{base, 0};
+  trunk_gws_layout(v->t, take);
+  v->smax = (unsigned*)take((int64_t)v->t.max_pairs * 4);
+  v->sc = (float*)take((int64_t)2 * v->t.max_pairs * 4);
+  return take.off;
 }
 
 // the network on 2n stacked images; the taps leave their partials behind (fin: their counts). feat_out: stop at tap stop_tap and return
@@ -748,38 +460,27 @@ int64_t lpips_gws_layout(gi_lpips* v, char* base) {
 int lpips_run(gi_lpips* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out, LpFinP& fin, bool grad = false) {
   hipStream_t st = v->ctx->stream;
   const int nimg = 2 * n;
-  int H = v->H, W = v->W, cur = 0;
-  half_t* curp = grad ? v->ga[0] : v->act[0];
+  int H = v->t.H, W = v->t.W, cur = 0;
+  half_t* curp = grad ? v->t.ga[0] : v->act[0];
   // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of gi_lpips_create)
-  GI_TRY(lp_conv1(st, xa, xb, n, H, W, v->wA, v->wB, v->params + v->boff[0], curp));
+  GI_TRY(lp_conv1(st, xa, xb, n, H, W, v->t.w1, v->wB, v->params + v->boff[0], curp));
   for (int i = 1; i < NCONV; ++i) {
-    half_t* outp = grad ? v->ga[i] : v->act[cur ^ 1];
-    GI_TRY(lp_conv3x3(st, curp, v->wpk[i], outp, nimg, H, W, kCin[i], kCout[i], v->params + v->boff[i]));
+    half_t* outp = grad ? v->t.ga[i] : v->act[cur ^ 1];
+    IgemmArgs a;
+    const int rc = conv3x3(st, curp, v->wpk[i], outp, nimg, H, W, kCin[i], kCout[i], v->params + v->boff[i], GI_ACT_RELU, 0, nullptr, nullptr, a);
+    if (rc == GI_ERR_UNSUPPORTED) gi_set_error("lpips: no mode-2 kernel serves n=%d %dx%d %d->%d", nimg, H, W, kCin[i], kCout[i]);
+    GI_TRY(rc);
     cur ^= 1;
     curp = outp;
     const int tap = kTapAfter[i], C = kCout[i];
     if (tap < 0) continue;
-    if (feat_out && tap == stop_tap) {
-      hipLaunchKernelGGL(lpips_nhwc_to_nchw_kernel, dim3(grid_for((int64_t)n * H * W * C, 256, 4096)), dim3(256), 0, st, curp, feat_out, n, H * W, C);
-      GI_LAUNCH_CHECK();
-      return GI_OK;
-    }
-    const bool pool = tap < NTAP - 1;
-    half_t* poolp = pool ? (grad ? v->gpool[i] : v->act[cur ^ 1]) : nullptr;
-    double* partial = v->partial + (int64_t)tap * v->max_pairs * LP_MAXNB;
+    if (feat_out && tap == stop_tap) return nhwc_to_nchw(st, curp, feat_out, n, H * W, C);
+    const bool pool = kPoolAfter[i] != 0;
+    half_t* poolp = pool ? (grad ? v->t.gpool[i] : v->act[cur ^ 1]) : nullptr;
+    double* partial = v->partial + (int64_t)tap * v->t.max_pairs * LP_MAXNB;
     fin.inv[tap] = 1.0 / ((double)H * W);
-#ifdef GI_LPIPS_UNFUSED
-    fin.nb[tap] = lp_tap_blocks(H, W, C, false);
-    GI_TRY(lp_tap(st, curp, n, H, W, C, v->params + v->linoff[tap], nullptr, partial));
-    if (pool) {
-      hipLaunchKernelGGL(lpips_maxpool2_kernel, dim3(grid_for((int64_t)nimg * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, curp, poolp, nimg,
-                         H / 2, W / 2, C);
-      GI_LAUNCH_CHECK();
-    }
-#else
     fin.nb[tap] = lp_tap_blocks(H, W, C, pool);
     GI_TRY(lp_tap(st, curp, n, H, W, C, v->params + v->linoff[tap], poolp, partial));
-#endif
     if (pool) { cur ^= 1; curp = poolp; H /= 2; W /= 2; }
   }
   return GI_OK;
@@ -789,59 +490,27 @@ int lpips_run(gi_lpips* v, const float* xa, const float* xb, int n, int stop_tap
 int lpips_seeds(gi_lpips* v, int n) {
   hipStream_t st = v->ctx->stream;
   for (int pass = 0; pass < 2; ++pass) {
-    int H = v->H, W = v->W;
+    int H = v->t.H, W = v->t.W;
     for (int i = 0; i < NCONV; ++i) {
       const int tap = kTapAfter[i];
-      if (tap < 0) continue;
-      GI_TRY(lp_seed(st, pass == 1, v->ga[i], n, (int64_t)H * W, kCout[i], v->params + v->linoff[tap], v->smax, v->sc));
-      if (tap < NTAP - 1) { H /= 2; W /= 2; }
+      if (tap >= 0) GI_TRY(lp_seed(st, pass == 1, v->t.ga[i], n, (int64_t)H * W, kCout[i], v->params + v->linoff[tap], v->smax, v->sc));
+      if (kPoolAfter[i]) { H /= 2; W /= 2; }
     }
-    if (pass == 0) GI_TRY(lp_scale(st, v->smax, v->sc, n));
+    if (pass == 0) GI_TRY(seed_scale(st, v->smax, v->sc, n));
   }
   return GI_OK;
 }
 
-// The chain from conv5_3 down. D_l = s_i * gradient w.r.t. the PRE-activation of layer l = [a_l > 0] * (transposed conv of D_(l+1), un-pooled
-// where a pool sits between, + s_i * seed_l at a tap). stop_tap < 0: down to D_0, then the first-layer adjoint into grad_out. stop_tap = t:
-// the gradient w.r.t. the post-ReLU map of tap t (no [a > 0] factor) goes to tap_out as NCHW fp32, de-scaled.
+// The chain from conv5_3 down (trunk_backward) on s_i * gradient; every tap below the top is a pooled layer, so its seed joins in the
+// un-pool. stop_tap < 0: down to the first-layer adjoint into grad_out. stop_tap = t: the gradient w.r.t. the post-ReLU map of tap t goes
+// to tap_out as NCHW fp32, de-scaled.
 int lpips_backward(gi_lpips* v, int n, int stop_tap, float* tap_out, float* grad_out, float gscale) {
-  hipStream_t st = v->ctx->stream;
-  int Hl[NCONV], Wl[NCONV], stop = -1;
-  {
-    int H = v->H, W = v->W;
-    for (int i = 0; i < NCONV; ++i) {
-      Hl[i] = H; Wl[i] = W;
-      if (kTapAfter[i] >= 0 && kTapAfter[i] == stop_tap) stop = i;
-      if (kTapAfter[i] >= 0 && kTapAfter[i] < NTAP - 1) { H /= 2; W /= 2; }
-    }
-  }
-  const float* sc_inv = v->sc + n;
-  auto seed_of = [&](int l) -> const half_t* { return kTapAfter[l] >= 0 ? v->ga[l] + (int64_t)n * Hl[l] * Wl[l] * kCout[l] : nullptr; };
-  auto readback = [&](const half_t* g, int l) -> int {
-    hipLaunchKernelGGL(lpips_nhwc_to_nchw_unscale_kernel, dim3(grid_for((int64_t)n * Hl[l] * Wl[l] * kCout[l], 256, 4096)), dim3(256), 0, st, g, sc_inv,
-                       tap_out, n, Hl[l] * Wl[l], kCout[l]);
-    GI_LAUNCH_CHECK();
-    return GI_OK;
-  };
-  int cur = 0;
-  const int top = NCONV - 1;
-  GI_TRY(lp_act_bwd(st, false, nullptr, v->ga[top], seed_of(top), v->gbuf[cur], n, Hl[top], Wl[top], kCout[top], stop != top));
-  if (stop == top) return readback(v->gbuf[cur], top);
-  for (int l = top; l >= 1; --l) {
-    const int below = l - 1;
-    const bool pool = kTapAfter[below] >= 0, last = stop == below;      // below < top: a tap below the top is a pooled layer
-    int applied = 0;
-    // the ReLU mask of the layer below in the GEMM epilogue, where the dispatched kernel has one
-    GI_TRY(lp_conv3x3_bwd(st, v->gbuf[cur], v->wT[l], v->gbuf[cur ^ 1], n, Hl[l], Wl[l], kCout[l], kCin[l], pool ? nullptr : v->ga[below], &applied));
-    if (pool) {
-      GI_TRY(lp_act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], seed_of(below), v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
-    } else {
-      cur ^= 1;
-      if (!applied) GI_TRY(lp_act_bwd(st, false, v->gbuf[cur], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], 1));
-    }
-    if (last) return readback(v->gbuf[cur], below);
-  }
-  return lp_conv1_adjoint(st, v->gbuf[cur], v->wA, sc_inv, gscale, grad_out, n, v->H, v->W);
+  int stop = -1;
+  for (int i = 0; i < NCONV; ++i)
+    if (kTapAfter[i] >= 0 && kTapAfter[i] == stop_tap) stop = i;
+  v->t.inv = v->sc + n;
+  v->t.inv_stride = 1;
+  return trunk_backward(v->t, v->ctx->stream, n, stop, tap_out, grad_out, gscale);
 }
 
 }  // namespace
@@ -854,7 +523,9 @@ int gi_lpips_create(gi_ctx* ctx, int H, int W, int max_pairs, gi_lpips** out) {
   GI_REQUIRE((int64_t)2 * max_pairs * H * W * 64 < (1ll << 31), "lpips_create: 2*%d images of %dx%d exceed 32-bit activation offsets", max_pairs, H, W);
   gi_lpips* v = new (std::nothrow) gi_lpips();
   GI_REQUIRE(v, "lpips_create: out of host memory");
-  v->ctx = ctx; v->H = H; v->W = W; v->max_pairs = max_pairs;
+  v->ctx = ctx;
+  v->t.nconv = NCONV; v->t.cin = kCin; v->t.cout = kCout; v->t.tap_after = kTapAfter; v->t.pool_after = kPoolAfter;
+  v->t.H = H; v->t.W = W; v->t.max_pairs = max_pairs;
   int64_t off = 0;
   for (int i = 0; i < NCONV; ++i) {
     v->woff[i] = off; off += (int64_t)kCout[i] * kCin[i] * 9;
@@ -913,19 +584,19 @@ int gi_lpips_bind(gi_lpips* v, const float* params, void* ws, int64_t ws_bytes) 
 int gi_lpips_sync_weights(gi_lpips* v) {
   GI_REQUIRE(v && v->bound, "lpips_sync_weights: not bound");
   hipStream_t st = v->ctx->stream;
-  GI_TRY(lp_fold(st, v->params + v->woff[0], v->params + v->shiftoff, v->params + v->scaleoff, v->wA, v->wB));
-  for (int i = 1; i < NCONV; ++i) GI_TRY(lp_pack3x3(st, v->params + v->woff[i], v->wpk[i], kCout[i], kCin[i]));
+  GI_TRY(lp_fold(st, v->params + v->woff[0], v->params + v->shiftoff, v->params + v->scaleoff, v->t.w1, v->wB));
+  for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, false, v->params + v->woff[i], v->wpk[i], kCout[i], kCin[i]));
   if (v->gbound)
-    for (int i = 1; i < NCONV; ++i) GI_TRY(lp_pack3x3_t(st, v->params + v->woff[i], v->wT[i], kCout[i], kCin[i]));
+    for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, true, v->params + v->woff[i], v->t.wT[i], kCout[i], kCin[i]));
   v->synced = true;
   return GI_OK;
 }
 
 int gi_lpips_distance(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n) {
   GI_REQUIRE(v && v->bound && v->synced, "lpips_distance: bind + sync_weights first");
-  GI_REQUIRE(a && b && out_n && n > 0 && n <= v->max_pairs, "lpips_distance: n=%d (max %d)", n, v->max_pairs);
+  GI_REQUIRE(a && b && out_n && n > 0 && n <= v->t.max_pairs, "lpips_distance: n=%d (max %d)", n, v->t.max_pairs);
   LpFinP fin = {};
-  fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->max_pairs;
+  fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->t.max_pairs;
   GI_TRY(lpips_run(v, a, b, n, -1, nullptr, fin));
   return lp_finish(v->ctx->stream, v->partial, fin, out_n, per_layer_5n);
 }
@@ -946,12 +617,12 @@ int gi_lpips_bind_grad(gi_lpips* v, void* ws, int64_t ws_bytes) {
 int gi_lpips_distance_grad(gi_lpips* v, const float* a, const float* b, int n, float* out_n, float* per_layer_5n, float* grad_a, float gscale) {
   GI_REQUIRE(v && v->gbound, "lpips_distance_grad: no grad workspace bound (gi_lpips_bind_grad)");
   GI_REQUIRE(v->bound && v->synced, "lpips_distance_grad: bind + sync_weights first");
-  GI_REQUIRE(a && b && out_n && grad_a && n > 0 && n <= v->max_pairs, "lpips_distance_grad: n=%d (max %d)", n, v->max_pairs);
+  GI_REQUIRE(a && b && out_n && grad_a && n > 0 && n <= v->t.max_pairs, "lpips_distance_grad: n=%d (max %d)", n, v->t.max_pairs);
   hipStream_t st = v->ctx->stream;
   v->grad_n = 0;
-  GI_HIP(hipMemsetAsync(v->smax, 0, (size_t)v->max_pairs * 4, st));
+  GI_HIP(hipMemsetAsync(v->smax, 0, (size_t)v->t.max_pairs * 4, st));
   LpFinP fin = {};
-  fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->max_pairs;
+  fin.ntap = NTAP; fin.n = n; fin.pair_stride = v->t.max_pairs;
   GI_TRY(lpips_run(v, a, b, n, -1, nullptr, fin, true));
   GI_TRY(lp_finish(st, v->partial, fin, out_n, per_layer_5n));
   GI_TRY(lpips_seeds(v, n));
@@ -969,7 +640,7 @@ int gi_lpips_grad_tap(gi_lpips* v, int tap, float* out_nchw_f32) {
 
 int gi_lpips_features(gi_lpips* v, const float* x, int n, int tap, float* out_nchw) {
   GI_REQUIRE(v && v->bound && v->synced, "lpips_features: bind + sync_weights first");
-  GI_REQUIRE(x && out_nchw && n > 0 && n <= v->max_pairs && tap >= 0 && tap < NTAP, "lpips_features: n=%d tap=%d", n, tap);
+  GI_REQUIRE(x && out_nchw && n > 0 && n <= v->t.max_pairs && tap >= 0 && tap < NTAP, "lpips_features: n=%d tap=%d", n, tap);
   LpFinP fin = {};
   // the runner works on 2n stacked images: feed x twice, return the first n
   return lpips_run(v, x, x, n, tap, out_nchw, fin);
@@ -1015,7 +686,7 @@ int gi_debug_lpips_tap(gi_ctx* ctx, const void* F, int n, int H, int W, int C, c
 int gi_debug_lpips_pack_t(gi_ctx* ctx, const float* w, void* out, int cout, int cin) {
   GI_REQUIRE(ctx && w && out, "debug_lpips_pack_t: null pointer");
   GI_REQUIRE(cout > 0 && cin > 0 && GI_LP_FITS31((int64_t)cout * 9 * cin), "debug_lpips_pack_t: cout=%d cin=%d", cout, cin);
-  return lp_pack3x3_t(ctx->stream, w, (half_t*)out, cout, cin);
+  return pack3x3(ctx->stream, true, w, (half_t*)out, cout, cin);
 }
 
 int gi_debug_lpips_seed(gi_ctx* ctx, int store, void* F, int n, int HW, int C, const float* lin, unsigned* smax, const float* sc) {
@@ -1028,7 +699,7 @@ int gi_debug_lpips_seed(gi_ctx* ctx, int store, void* F, int n, int HW, int C, c
 
 int gi_debug_lpips_scale(gi_ctx* ctx, const unsigned* smax, float* sc, int n) {
   GI_REQUIRE(ctx && smax && sc && n > 0, "debug_lpips_scale: null pointer or n=%d", n);
-  return lp_scale(ctx->stream, smax, sc, n);
+  return seed_scale(ctx->stream, smax, sc, n);
 }
 
 int gi_debug_lpips_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W, int C, int relu) {
@@ -1038,14 +709,14 @@ int gi_debug_lpips_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act
   GI_REQUIRE(!pool || (g && out != g && H % 2 == 0 && W % 2 == 0), "debug_lpips_act_bwd: the pool form needs g, out apart from g and even H=%d W=%d", H, W);
   GI_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)act & 15) == 0 && ((uintptr_t)seed & 15) == 0 && ((uintptr_t)out & 15) == 0,
              "debug_lpips_act_bwd: g, act, seed and out must be 16-byte aligned");
-  return lp_act_bwd(ctx->stream, pool != 0, (const half_t*)g, (const half_t*)act, (const half_t*)seed, (half_t*)out, n, H, W, C, relu);
+  return act_bwd(ctx->stream, pool != 0, (const half_t*)g, (const half_t*)act, (const half_t*)seed, (half_t*)out, n, H, W, C, relu);
 }
 
 int gi_debug_lpips_conv1_adjoint(gi_ctx* ctx, const void* D, const float* wA, const float* sc_inv, float gscale, float* dimg, int n, int H, int W) {
   GI_REQUIRE(ctx && D && wA && sc_inv && dimg, "debug_lpips_conv1_adjoint: null pointer");
   GI_REQUIRE(n > 0 && H > 0 && W > 0 && GI_LP_FITS31((int64_t)n * H * W * 64), "debug_lpips_conv1_adjoint: n=%d H=%d W=%d", n, H, W);
   GI_REQUIRE(((uintptr_t)D & 15) == 0, "debug_lpips_conv1_adjoint: D must be 16-byte aligned");
-  return lp_conv1_adjoint(ctx->stream, (const half_t*)D, wA, sc_inv, gscale, dimg, n, H, W);
+  return conv1_adjoint(ctx->stream, (const half_t*)D, wA, sc_inv, 1, gscale, dimg, n, H, W);
 }
 
 }  // extern "C"

@@ -9,15 +9,17 @@
 // `output` and `target` run as ONE stacked batch of 2n images (NHWC fp16):
 //   conv1_1  the input is the grey image repeated over 3 channels (loss.py:54-55), so the 3->64 conv is
 //            a 1->64 conv with the weights summed over the input channel: one HBM-bound VALU kernel;
-//   12 more  3x3/s1/p1 convolutions + bias + ReLU: igemm3 mode 2 (fp16 MFMA implicit GEMM, LDS-DMA ring);
-//   2x2 max pooling: 16-byte NHWC kernel;
+//   12 more  3x3/s1/p1 convolutions + bias + ReLU: igemm3 mode 2 (fp16 MFMA implicit GEMM, LDS-DMA ring; vggtrunk.hip's conv3x3);
+//   2x2 max pooling: 16-byte NHWC kernel (vggtrunk.hip's maxpool2);
 //   taps     perceptual term mean((F_o - F_t)^2) and the Gram matrices F^T F / (H W C) (MFMA GEMM with K = pixels,
 //            both operands pixel-major: transposing LDS reads as in wgrad.hip) in ONE pass per tap over the
 //            image pairs (gram2_kernel: partial tiles, no atomics), then mean((G_o - G_t)^2) from the
 //            partial tiles in a fixed order; one finish launch for all ten terms.
+// The trunk's shared pieces (weight packing, pooling, read-backs, and the backward's scale, activation backward, first-layer adjoint,
+// workspace arenas and chain) are vggtrunk.hip's, which LPIPS (lpips.hip) runs too.
 #include <new>
 
-#include "common.h"
+#include "vggtrunk.h"
 
 namespace {
 
@@ -29,16 +31,6 @@ const int kFeatIdx[NCONV] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28};   
 const int kTapAfter[NCONV] = {0, -1, 1, -1, 2, -1, -1, -1, 3, -1, -1, -1, 4};
 const int kPoolAfter[NCONV] = {0, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0};
 
-// [cout][cin][3][3] fp32 -> fp16 [cout][tap][cin]
-__global__ void __launch_bounds__(256) pack3x3_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
-  const int64_t total = (int64_t)cout * 9 * cin;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int c = (int)(i % cin);
-    const int t = (int)((i / cin) % 9);
-    const int o = (int)(i / ((int64_t)cin * 9));
-    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + t];
-  }
-}
 // conv1_1 on a channel-replicated grey image: w1[o][tap] = sum_c w[o][c][tap]
 __global__ void __launch_bounds__(256) sum_cin_kernel(const float* __restrict__ w, float* __restrict__ w1, int cout, int cin) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -115,25 +107,6 @@ __global__ void __launch_bounds__(256) vgg_conv1_mfma_kernel(const float* __rest
     *(h8_t*)(dst + 32 + kq * 8) = o[1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) bv[j] = bn[j];
-  }
-}
-
-// NHWC fp16 2x2 / stride 2 max pooling, 8 channels per thread
-__global__ void __launch_bounds__(256) maxpool2_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int nimg, int Ho, int Wo,
-                                                       int C) {
-  const int cg = C / 8;
-  const int64_t total = (int64_t)nimg * Ho * Wo * cg;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int g = (int)(i % cg);
-    const int64_t p = i / cg;
-    const int x = (int)(p % Wo);
-    const int64_t t = p / Wo;
-    const int y = (int)(t % Ho);
-    const int64_t img = t / Ho;
-    const half_t* s = in + (((img * 2 * Ho + 2 * y) * 2 * Wo + 2 * x) * (int64_t)C) + g * 8;
-    const h8_t a = *(const h8_t*)s, b = *(const h8_t*)(s + C);
-    const h8_t c = *(const h8_t*)(s + (int64_t)2 * Wo * C), d = *(const h8_t*)(s + (int64_t)2 * Wo * C + C);
-    *(h8_t*)(out + p * C + g * 8) = __builtin_elementwise_max(__builtin_elementwise_max(a, b), __builtin_elementwise_max(c, d));
   }
 }
 
@@ -332,36 +305,13 @@ __global__ void __launch_bounds__(256) vgg_finish_kernel(const double* __restric
     out2[1] = ws * ss;
   }
 }
-// NHWC fp16 feature map -> NCHW fp32 (parity / debugging)
-__global__ void __launch_bounds__(256) nhwc_to_nchw_f32_kernel(const half_t* __restrict__ in, float* __restrict__ out, int nimg, int HW, int C) {
-  const int64_t total = (int64_t)nimg * HW * C;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const int64_t t = i / HW;
-    const int c = (int)(t % C);
-    const int64_t img = t / C;
-    out[i] = (float)in[(img * HW + p) * C + c];
-  }
-}
-
 
 // ================================================================================================================================
 // Opt-in backward: d(weight_p * P + weight_s * S) / d(output), target constant. Everything runs on s * gradient in fp16 with
-// fp32 accumulation, s = 2^k chosen on the device from the largest seed (vgg_scale_kernel) and removed in fp32 by the last kernel.
+// fp32 accumulation, s = 2^k chosen on the device from the largest seed (vggtrunk.hip's seed_scale_kernel, n = 1) and removed in fp32 by
+// the last kernel. This file holds the seeds; the chain below them is vggtrunk.hip's trunk_backward.
 // No float atomics: the only atomic is an unsigned max over bit patterns of non-negative floats, whose result does not depend on order.
 // ================================================================================================================================
-
-// [cout][cin][3][3] fp32 -> fp16 [cin][tap'][cout] with tap' = 8 - tap: the transpose of a 3x3 / s1 / p1 convolution is that convolution
-// with the taps reversed and the channel roles exchanged, so the input-gradient GEMMs run on the forward's mode-2 kernels
-__global__ void __launch_bounds__(256) pack3x3_t_kernel(const float* __restrict__ w, half_t* __restrict__ out, int cout, int cin) {
-  const int64_t total = (int64_t)cin * 9 * cout;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int o = (int)(i % cout);
-    const int t = (int)((i / cout) % 9);
-    const int c = (int)(i / ((int64_t)cout * 9));
-    out[i] = (half_t)w[((int64_t)o * cin + c) * 9 + (8 - t)];
-  }
-}
 
 // max over a 256-thread workgroup, then ONE unsigned atomic max per workgroup (bit patterns of non-negative floats order like the
 // floats; a maximum does not depend on the order of its operands, so the result is the same in every run)
@@ -424,7 +374,7 @@ __global__ void __launch_bounds__(256) gram_delta_kernel(const float* __restrict
 // STORE = false: max |seed| only - the magnitude the scale s is chosen from. Maps of more than kSeedSampleAll pixel blocks per image
 // are SAMPLED: one block of every eight (block 8 j + (3 j mod 8): all column positions, spread over the rows), so that this pass
 // costs an eighth of the store pass where the maps are large. The sample can only under-estimate the maximum; the headroom of
-// kSeedExp covers that.
+// kSeedExp (vggtrunk.hip) covers that.
 struct SeedP {
   const half_t* Fo; half_t* Ft; const float* dg; const unsigned* dmax; unsigned* smax; const float* sc;
   int C, HW, nb; float cp, cs;      // nb: 256-pixel blocks per image
@@ -502,157 +452,10 @@ __global__ void __launch_bounds__(256) vgg_seed_kernel(SeedP p) {
   }
   if (!STORE) amax_commit_block(m, red, p.smax);
 }
-// s = 2^(kSeedExp - e) with max |seed| = m * 2^e, m in [0.5, 1): the largest seed lands in [2^(kSeedExp-1), 2^kSeedExp). All seeds zero
-// (output == target) or a non-finite maximum: s = 1. kSeedExp = -2: with the stand-in weights the largest gradient of
-// any layer stays within 2x the largest seed (fp64 oracle, 64x64 and 48x80), so 2^-2 leaves a factor 2^18 up to fp16's 65504 for
-// weights that amplify more, and 12 binades of normal numbers (22 with subnormals) below the maximum.
-constexpr int kSeedExp = -2;
-__global__ void vgg_scale_kernel(const unsigned* __restrict__ smax, float* __restrict__ sc) {
-  const float am = __uint_as_float(*smax);
-  int ex = 0;
-  float s = 1.f;
-  if (am > 0.f && am < INFINITY) {
-    (void)frexpf(am, &ex);
-    int k = kSeedExp - ex;
-    k = k > 100 ? 100 : (k < -100 ? -100 : k);
-    s = ldexpf(1.f, k);
-  }
-  sc[0] = s;
-  sc[1] = 1.f / s;
-}
 
-// Fused activation backward between two input-gradient GEMMs, 16-byte NHWC accesses, 8 channels per thread:
-//   POOL = false: out = [act > 0] * (g + seed)                     (g and / or seed may be null; out may alias g)
-//   POOL = true:  g lives on the (H/2, W/2) grid: every 2x2 window of `act` routes its value to the first maximum in row-major
-//                 order (F.max_pool2d's backward), times [act > 0]; the other three positions are written as zeros
-// relu = 0 drops the [act > 0] factor: the gradient w.r.t. the post-ReLU map itself (gi_vgg19_grad_layer).
-template <bool POOL>
-__global__ void __launch_bounds__(256) vgg_act_bwd_kernel(const half_t* g, const half_t* __restrict__ act, const half_t* __restrict__ seed,
-                                                          half_t* out, int nimg, int H, int W, int C, int relu) {
-  const int cg = C / 8;
-  const h8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  if constexpr (!POOL) {
-    const int64_t total = (int64_t)nimg * H * W * cg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-      const h8_t a = *(const h8_t*)(act + i * 8);
-      const h8_t gv = g ? *(const h8_t*)(g + i * 8) : z8;
-      const h8_t sv = seed ? *(const h8_t*)(seed + i * 8) : z8;
-      h8_t o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (!relu || (float)a[e] > 0.f) ? (half_t)((float)gv[e] + (float)sv[e]) : (half_t)0.f;
-      *(h8_t*)(out + i * 8) = o;
-    }
-  } else {
-    const int Ho = H / 2, Wo = W / 2;
-    const int64_t total = (int64_t)nimg * Ho * Wo * cg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-      const int gq = (int)(i % cg);
-      const int64_t pq = i / cg;
-      const int x = (int)(pq % Wo);
-      const int64_t tt = pq / Wo;
-      const int y = (int)(tt % Ho);
-      const int64_t img = tt / Ho;
-      const int64_t o00 = (((img * H + 2 * y) * W + 2 * x) * (int64_t)C) + gq * 8;
-      const int64_t off[4] = {o00, o00 + C, o00 + (int64_t)W * C, o00 + (int64_t)W * C + C};
-      h8_t a[4], o[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] = *(const h8_t*)(act + off[q]);
-      const h8_t gv = *(const h8_t*)(g + pq * C + gq * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        int best = 0;
-        float bv = (float)a[0][e];
-#pragma unroll
-        for (int q = 1; q < 4; ++q) { const float av = (float)a[q][e]; if (av > bv) { bv = av; best = q; } }
-        const half_t val = (!relu || bv > 0.f) ? gv[e] : (half_t)0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q][e] = q == best ? val : (half_t)0.f;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(h8_t*)(out + off[q]) = o[q];
-    }
-  }
-}
+// ---- host launch code of this file's kernels: one copy of every grid rule, shared by the network runners below and the
+// gi_debug_vgg_* entries (the trunk's: vggtrunk.h) ------------------------------------------------------------------------------------
 
-// conv1_1 adjoint: dimg[n][y][x] = mul * sum_{ky,kx,o} w1[o][ky][kx] * D[n][y+1-ky][x+1-kx][o] (the grey image feeds all three input
-// channels, so the weights are sum_cin_kernel's w1, in fp32), mul = gscale / s with s from device memory: the fp16 scale leaves here.
-// A workgroup owns a 16 x 32 pixel tile: its threads reduce the 64 channels of each of the 18 x 34 halo pixels of D to nine per-tap
-// sums T[tap] (one pass over D: 128 bytes per pixel in 16-byte loads, the weights through wave-uniform addresses) into LDS, then
-// every output pixel adds its nine neighbours' sums. HBM-bound: D is read once plus the halo (20 %, mostly from L2).
-__global__ void __launch_bounds__(256) vgg_conv1_adjoint_kernel(const half_t* __restrict__ D, const float* __restrict__ w1, const float* __restrict__ sc,
-                                                                float gscale, float* __restrict__ dimg, int H, int W) {
-  constexpr int TH = 16, TW = 32, HH = TH + 2, HW_ = TW + 2, NH = HH * HW_;
-  __shared__ float T[NH * 9];
-  const int img = blockIdx.z, y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
-  const half_t* Di = D + (int64_t)img * H * W * 64;
-  for (int h = threadIdx.x; h < NH; h += 256) {
-    const int hy = h / HW_, hx = h - hy * HW_;
-    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-    float t[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t[k] = 0.f;
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      const half_t* src = Di + ((int64_t)y * W + x) * 64;
-      h8_t v[8];
-#pragma unroll
-      for (int c8 = 0; c8 < 8; ++c8) v[c8] = *(const h8_t*)(src + c8 * 8);
-#pragma unroll
-      for (int c8 = 0; c8 < 8; ++c8)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = (float)v[c8][e];
-#pragma unroll
-          for (int k = 0; k < 9; ++k) t[k] = fmaf(w1[(c8 * 8 + e) * 9 + k], d, t[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) T[h * 9 + k] = t[k];
-  }
-  __syncthreads();
-  const float mul = gscale * sc[1];
-  for (int o = threadIdx.x; o < TH * TW; o += 256) {
-    const int ty = o / TW, tx = o - ty * TW;
-    const int y = y0 + ty, x = x0 + tx;
-    if (y >= H || x >= W) continue;
-    float s = 0.f;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) s += T[((ty + 2 - ky) * HW_ + (tx + 2 - kx)) * 9 + ky * 3 + kx];
-    dimg[((int64_t)img * H + y) * W + x] = s * mul;
-  }
-}
-// NHWC fp16 (s * gradient) -> NCHW fp32 gradient (gi_vgg19_grad_layer)
-__global__ void __launch_bounds__(256) nhwc_to_nchw_unscale_kernel(const half_t* __restrict__ in, const float* __restrict__ sc, float* __restrict__ out,
-                                                                   int nimg, int HW, int C) {
-  const int64_t total = (int64_t)nimg * HW * C;
-  const float inv = sc[1];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const int64_t t = i / HW;
-    const int c = (int)(t % C);
-    const int64_t img = t / C;
-    out[i] = (float)in[(img * HW + p) * C + c] * inv;
-  }
-}
-
-int nblk(int64_t work, int per, int cap) {
-  int64_t b = (work + per - 1) / per;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// ---- host launch code: one copy of every grid rule, shared by the network runners below and the gi_debug_vgg_* entries --------------
-
-// fp32 master weights -> what the mode-2 kernels read: [cout][tap][cin], or (transposed) [cin][8 - tap][cout]
-int pack3x3(hipStream_t st, bool transposed, const float* w, half_t* out, int cout, int cin) {
-  const dim3 grid(nblk((int64_t)cout * 9 * cin, 256, 2048));
-  if (transposed) hipLaunchKernelGGL(pack3x3_t_kernel, grid, dim3(256), 0, st, w, out, cout, cin);
-  else hipLaunchKernelGGL(pack3x3_kernel, grid, dim3(256), 0, st, w, out, cout, cin);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
 int sum_cin(hipStream_t st, const float* w, float* w1) {
   hipLaunchKernelGGL(sum_cin_kernel, dim3(3), dim3(256), 0, st, w, w1, 64, 3);
   GI_LAUNCH_CHECK();
@@ -660,30 +463,7 @@ int sum_cin(hipStream_t st, const float* w, float* w1) {
 }
 // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of the callers)
 int conv1(hipStream_t st, const float* xa, const float* xb, int n, int H, int W, const float* w1, const float* bias, half_t* out) {
-  hipLaunchKernelGGL(vgg_conv1_mfma_kernel, dim3(nblk((int64_t)2 * n * H * (W / 16), 4, 256 * 8)), dim3(256), 0, st, xa, xb, n, H, W, w1, bias, out);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-// one 3x3 / s1 / p1 convolution on the mode-2 kernels; mask (with the optional addend): the ReLU mask of the result's layer in the
-// epilogue, where the dispatched kernel has one. `a` returns pool_applied / mask_applied.
-int conv3x3(hipStream_t st, const half_t* in, const half_t* w, half_t* out, int nimg, int H, int W, int cin, int cout, const float* bias, int act_out,
-            int pool2, const half_t* mask, const half_t* add, IgemmArgs& a) {
-  a = IgemmArgs{};
-  a.in = in; a.w = w; a.out = out;
-  a.bias = bias; a.partials = nullptr; a.ws = nullptr; a.ws_bytes = 0;
-  a.n = nimg; a.Hs = H; a.Ws = W;
-  a.cin = cin; a.ldin = cin; a.coffin = 0;
-  a.cout = cout; a.ldout = cout; a.coffout = 0;
-  a.relu_in = 0; a.relu_cend = 0; a.act_out = act_out; a.force_splitk = 0;
-  a.pool2 = pool2;
-  if (mask) {
-    a.mask = mask; a.ldmask = cout; a.coffmask = 0; a.mask_slope = 0.f;
-    a.add = add; a.ldadd = cout; a.coffadd = 0;
-  }
-  return op_igemm(st, GI_F16, 2, a);
-}
-int maxpool2(hipStream_t st, const half_t* in, half_t* out, int nimg, int Ho, int Wo, int C) {
-  hipLaunchKernelGGL(maxpool2_kernel, dim3(nblk((int64_t)nimg * Ho * Wo * (C / 8), 256, 8192)), dim3(256), 0, st, in, out, nimg, Ho, Wo, C);
+  hipLaunchKernelGGL(vgg_conv1_mfma_kernel, dim3(grid_for((int64_t)2 * n * H * (W / 16), 4, 256 * 8)), dim3(256), 0, st, xa, xb, n, H, W, w1, bias, out);
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
@@ -717,7 +497,7 @@ int tap_terms(hipStream_t st, const half_t* F, int n, int64_t HW, int C, int tap
   GI_LAUNCH_CHECK();
   fin.nb[tap] = n * nb_ * split;
   fin.inv[tap] = 1.0 / (double)((int64_t)n * HW * C);
-  const int nb2 = nblk((int64_t)n * ntile * BLK * BLK / 64, 1, 1024);
+  const int nb2 = grid_for((int64_t)n * ntile * BLK * BLK / 64, 1, 1024);
   hipLaunchKernelGGL(gram2_diff_kernel, dim3(nb2), dim3(256), 0, st, (const float*)gram, n, nb_, ntile, split, BLK * BLK,
                      (float)(1.0 / ((double)HW * C)), partial + (5 + tap) * 1024);
   GI_LAUNCH_CHECK();
@@ -752,32 +532,12 @@ int seed_pass(hipStream_t st, bool store, const half_t* Fo, half_t* Ft, const fl
   GI_LAUNCH_CHECK();
   return GI_OK;
 }
-int seed_scale(hipStream_t st, const unsigned* smax, float* sc) {
-  hipLaunchKernelGGL(vgg_scale_kernel, dim3(1), dim3(1), 0, st, smax, sc);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-int act_bwd(hipStream_t st, bool pool, const half_t* g, const half_t* act, const half_t* seed, half_t* out, int n, int H, int W, int C, int relu) {
-  if (pool) {
-    hipLaunchKernelGGL(vgg_act_bwd_kernel<true>, dim3(nblk((int64_t)n * (H / 2) * (W / 2) * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H,
-                       W, C, relu);
-  } else {
-    hipLaunchKernelGGL(vgg_act_bwd_kernel<false>, dim3(nblk((int64_t)n * H * W * (C / 8), 256, 8192)), dim3(256), 0, st, g, act, seed, out, n, H, W, C, relu);
-  }
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
-int conv1_adjoint(hipStream_t st, const half_t* D, const float* w1, const float* sc, float gscale, float* dimg, int n, int H, int W) {
-  hipLaunchKernelGGL(vgg_conv1_adjoint_kernel, dim3((W + 31) / 32, (H + 15) / 16, n), dim3(256), 0, st, D, w1, sc, gscale, dimg, H, W);
-  GI_LAUNCH_CHECK();
-  return GI_OK;
-}
 
 }  // namespace
 
 struct gi_vgg {
   gi_ctx* ctx;
-  int H, W, max_pairs;
+  VggTrunk t;             // H, W, max_pairs; w1: conv1_1 summed weights [64][9]; the rest only with the grad workspace
   int64_t woff[NCONV], boff[NCONV];   // float offsets into params
   int64_t param_floats;
   const float* params;
@@ -786,7 +546,6 @@ struct gi_vgg {
   int64_t ws_bytes;
   half_t* act[2];
   half_t* wpk[NCONV];     // [1..12] packed fp16 weights
-  float* w1;              // conv1_1 summed weights [64][9]
   float* gram;            // partial Gram tiles (gram2_kernel): gram_bytes
   int64_t gram_bytes;
   double* partial;        // [10 terms][1024] doubles
@@ -798,76 +557,41 @@ struct gi_vgg {
   int64_t gws_bytes;
   bool gbound;
   int grad_n;             // pairs of the last grad call (0: none yet): gi_vgg19_grad_layer replays its backward
-  half_t* ga[NCONV];      // post-ReLU maps, [output half | target half]; the target half survives only at the taps
-  half_t* gpool[NCONV];   // 2x2 max pool of the pooled layers (both halves): the next layer's input
-  half_t* wT[NCONV];      // [1..12] fp16 weights of the transposed convolutions: [cin][reversed tap][cout]
-  half_t* gbuf[2];        // gradient ping-pong (n images)
   float* dgram[5];        // per tap: dense G_o - G_t, [pairs][C][C] fp32
   unsigned* amax;         // [0..4] max |G_o - G_t| per tap, [5] max |seed| over the taps (bit patterns of non-negative floats)
-  float* sc;              // [0] = s = 2^k, [1] = 1 / s: the backward runs on s * gradient
+  float* sc;              // [0] = s = 2^k, [1] = 1 / s (t.inv, stride 0): the backward runs on s * gradient
 };
 
 namespace {
 
-// grad workspace. The forward's maps go to two arenas, alternating per stage (convolution or pooling): a stage reads the other arena
-// and writes [output half | target half] behind what its arena must keep - the output halves of the 13 convolutions (ReLU masks,
-// pool routing) and both halves at the five taps - so a target half nobody needs is overwritten by the stage after next.
+// grad workspace: the trunk's arenas, transposed weights and gradient buffers (the [output half | target half] maps of trunk_gws_layout),
+// then the dense Gram differences and the two small arrays of the seeds
 int64_t vgg_gws_layout(gi_vgg* v, char* base) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
-  int64_t pos[2] = {0, 0}, ext[2] = {0, 0}, start[2 * NCONV];
-  int H = v->H, W = v->W, k = 0;
-  for (int i = 0; i < NCONV; ++i) {
-    const int64_t half = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
-    start[2 * i] = pos[k & 1];
-    if (start[2 * i] + 2 * half > ext[k & 1]) ext[k & 1] = start[2 * i] + 2 * half;
-    pos[k & 1] += half * (kTapAfter[i] >= 0 ? 2 : 1);
-    ++k;
-    start[2 * i + 1] = -1;
-    if (kPoolAfter[i]) {
-      H /= 2; W /= 2;
-      start[2 * i + 1] = pos[k & 1];       // kept by nobody: the next stage of this arena starts at the same place
-      const int64_t ph = (int64_t)v->max_pairs * H * W * kCout[i] * 2;
-      if (start[2 * i + 1] + 2 * ph > ext[k & 1]) ext[k & 1] = start[2 * i + 1] + 2 * ph;
-      ++k;
-    }
-  }
-  char* arena[2];
-  arena[0] = take(ext[0]);
-  arena[1] = take(ext[1]);
-  for (int i = 0, kk = 0; i < NCONV; ++i) {
-    v->ga[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i]) : nullptr;
-    ++kk;
-    v->gpool[i] = nullptr;
-    if (kPoolAfter[i]) { v->gpool[i] = base ? (half_t*)(arena[kk & 1] + start[2 * i + 1]) : nullptr; ++kk; }
-  }
-  v->wT[0] = nullptr;
-  for (int i = 1; i < NCONV; ++i) v->wT[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
-  const int64_t gbytes = (int64_t)v->max_pairs * v->H * v->W * 64 * 2;
-  v->gbuf[0] = (half_t*)take(gbytes);
-  v->gbuf[1] = (half_t*)take(gbytes);
+  WsTake take{base, 0};
+  trunk_gws_layout(v->t, take);
   const int tapC[5] = {64, 128, 256, 512, 512};
-  for (int t = 0; t < 5; ++t) v->dgram[t] = (float*)take((int64_t)v->max_pairs * tapC[t] * tapC[t] * 4);
+  for (int t = 0; t < 5; ++t) v->dgram[t] = (float*)take((int64_t)v->t.max_pairs * tapC[t] * tapC[t] * 4);
   v->amax = (unsigned*)take(256);
   v->sc = (float*)take(256);
-  return off;
+  v->t.inv = v->sc ? v->sc + 1 : nullptr;
+  v->t.inv_stride = 0;
+  return take.off;
 }
 
 int64_t vgg_ws_layout(gi_vgg* v, char* base) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += gi_align_up(bytes, 256); return p; };
-  const int64_t act_bytes = (int64_t)2 * v->max_pairs * v->H * v->W * 64 * 2;
+  WsTake take{base, 0};
+  const int64_t act_bytes = (int64_t)2 * v->t.max_pairs * v->t.H * v->t.W * 64 * 2;
   v->act[0] = (half_t*)take(act_bytes);
   v->act[1] = (half_t*)take(act_bytes);
   v->wpk[0] = nullptr;
   for (int i = 1; i < NCONV; ++i) v->wpk[i] = (half_t*)take((int64_t)kCout[i] * 9 * kCin[i] * 2);
-  v->w1 = (float*)take(64 * 9 * 4);
-  v->gram_bytes = (int64_t)2 * v->max_pairs * 10 * 65536;          // one split of the widest tap (ten 128 x 128 tiles per image)
+  v->t.w1 = (float*)take(64 * 9 * 4);
+  v->gram_bytes = (int64_t)2 * v->t.max_pairs * 10 * 65536;          // one split of the widest tap (ten 128 x 128 tiles per image)
   if (v->gram_bytes < (32ll << 20)) v->gram_bytes = 32ll << 20;
   v->gram = (float*)take(v->gram_bytes);
   v->partial = (double*)take(10 * 1024 * 8);
   v->per_tap = (float*)take(64);
-  return off;
+  return take.off;
 }
 
 // grad: every layer writes its own map in the grad workspace (nothing is overwritten that the backward reads), the pooled layers keep
@@ -875,15 +599,15 @@ int64_t vgg_ws_layout(gi_vgg* v, char* base) {
 int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, float* feat_out, bool grad = false) {
   hipStream_t st = v->ctx->stream;
   const int nimg = 2 * n;
-  int H = v->H, W = v->W, cur = 0;
-  half_t* curp = grad ? v->ga[0] : v->act[0];
+  int H = v->t.H, W = v->t.W, cur = 0;
+  half_t* curp = grad ? v->t.ga[0] : v->act[0];
   // (W % 16 == 0 and 2 n H W 64 < 2^31 are conditions of gi_vgg19_create)
-  GI_TRY(conv1(st, xa, xb, n, H, W, v->w1, v->params + v->boff[0], curp));
+  GI_TRY(conv1(st, xa, xb, n, H, W, v->t.w1, v->params + v->boff[0], curp));
   for (int i = 0; i < NCONV; ++i) {
     bool pooled = false;
     if (i > 0) {
       IgemmArgs a;
-      half_t* outp = grad ? v->ga[i] : v->act[cur ^ 1];
+      half_t* outp = grad ? v->t.ga[i] : v->act[cur ^ 1];
       // the pooled layers (conv1_2, conv2_2, conv3_4, conv4_4) are never taps: where the kernel can, it stores the 2x2 max pool of
       // its tile and the full-resolution map is never written
       const int pool2 = (!grad && kPoolAfter[i] && kTapAfter[i] < 0) ? 1 : 0;
@@ -897,11 +621,7 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
     if (tap >= 0) {
       const half_t* F = curp;
       const int64_t HW = (int64_t)H * W;
-      if (feat_out && tap == stop_tap) {
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(nblk((int64_t)n * HW * C, 256, 4096)), dim3(256), 0, st, F, feat_out, n, (int)HW, C);
-        GI_LAUNCH_CHECK();
-        return GI_OK;
-      }
+      if (feat_out && tap == stop_tap) return nhwc_to_nchw(st, F, feat_out, n, (int)HW, C);
       if (!feat_out) {
         // perceptual term mean over (n, C, H, W) of (F_o - F_t)^2 and style term mean over (n, C, C) of (G_o - G_t)^2, G = F^T F / (HW C):
         // one pass over the tap's feature maps (gram2_kernel) + the fixed-order reduction of its partial tiles
@@ -913,8 +633,8 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
       H /= 2;
       W /= 2;
     } else if (kPoolAfter[i]) {
-      GI_TRY(maxpool2(st, curp, grad ? v->gpool[i] : v->act[cur ^ 1], nimg, H / 2, W / 2, C));
-      curp = grad ? v->gpool[i] : v->act[cur ^ 1];
+      GI_TRY(maxpool2(st, curp, grad ? v->t.gpool[i] : v->act[cur ^ 1], nimg, H / 2, W / 2, C));
+      curp = grad ? v->t.gpool[i] : v->act[cur ^ 1];
       cur ^= 1;
       H /= 2;
       W /= 2;
@@ -927,54 +647,19 @@ int vgg_run(gi_vgg* v, const float* xa, const float* xb, int n, int stop_tap, fl
 int vgg_seeds(gi_vgg* v, int n, float weight_p, float weight_s) {
   hipStream_t st = v->ctx->stream;
   for (int pass = 0; pass < 2; ++pass) {
-    int H = v->H, W = v->W;
+    int H = v->t.H, W = v->t.W;
     for (int i = 0; i < NCONV; ++i) {
       const int tap = kTapAfter[i], C = kCout[i];
       if (tap >= 0) {
         const int64_t HW = (int64_t)H * W;
-        GI_TRY(seed_pass(st, pass == 1, v->ga[i], v->ga[i] + (int64_t)n * HW * C, v->dgram[tap], v->amax + tap, v->amax + 5, v->sc, n, HW, C, weight_p,
+        GI_TRY(seed_pass(st, pass == 1, v->t.ga[i], v->t.ga[i] + (int64_t)n * HW * C, v->dgram[tap], v->amax + tap, v->amax + 5, v->sc, n, HW, C, weight_p,
                          weight_s));
       }
       if (kPoolAfter[i]) { H /= 2; W /= 2; }
     }
-    if (pass == 0) GI_TRY(seed_scale(st, v->amax + 5, v->sc));
+    if (pass == 0) GI_TRY(seed_scale(st, v->amax + 5, v->sc, 1));
   }
   return GI_OK;
-}
-
-// The chain from conv5_1 down. D_l = s * gradient w.r.t. the PRE-activation of layer l = [a_l > 0] * (transposed conv of D_(l+1), un-pooled
-// where a pool sits between, + seed_l at a tap). stop < 0: down to D_0, then the conv1_1 adjoint into grad_out. stop = L: the gradient
-// w.r.t. the post-ReLU map of layer L (no [a_L > 0] factor) goes to layer_out as NCHW fp32, de-scaled.
-int vgg_backward(gi_vgg* v, int n, int stop, float* layer_out, float* grad_out, float gscale) {
-  hipStream_t st = v->ctx->stream;
-  int Hl[NCONV], Wl[NCONV];
-  { int H = v->H, W = v->W; for (int i = 0; i < NCONV; ++i) { Hl[i] = H; Wl[i] = W; if (kPoolAfter[i]) { H /= 2; W /= 2; } } }
-  auto seed_of = [&](int l) -> const half_t* { return kTapAfter[l] >= 0 ? v->ga[l] + (int64_t)n * Hl[l] * Wl[l] * kCout[l] : nullptr; };
-  auto readback = [&](const half_t* g, int l) -> int {
-    hipLaunchKernelGGL(nhwc_to_nchw_unscale_kernel, dim3(nblk((int64_t)n * Hl[l] * Wl[l] * kCout[l], 256, 4096)), dim3(256), 0, st, g, (const float*)v->sc,
-                       layer_out, n, Hl[l] * Wl[l], kCout[l]);
-    GI_LAUNCH_CHECK();
-    return GI_OK;
-  };
-  int cur = 0;
-  GI_TRY(act_bwd(st, false, nullptr, v->ga[NCONV - 1], seed_of(NCONV - 1), v->gbuf[cur], n, Hl[NCONV - 1], Wl[NCONV - 1], kCout[NCONV - 1], stop != NCONV - 1));
-  if (stop == NCONV - 1) return readback(v->gbuf[cur], NCONV - 1);
-  for (int l = NCONV - 1; l >= 1; --l) {
-    const int below = l - 1;
-    const bool pool = kPoolAfter[below] != 0, last = stop == below;
-    IgemmArgs a;
-    const bool fuse = !pool && !last;     // the ReLU mask of the layer below (+ its seed) in the GEMM epilogue, where the dispatched kernel has one
-    GI_TRY(conv3x3(st, v->gbuf[cur], v->wT[l], v->gbuf[cur ^ 1], n, Hl[l], Wl[l], kCout[l], kCin[l], nullptr, GI_ACT_NONE, 0, fuse ? v->ga[below] : nullptr,
-                   fuse ? seed_of(below) : nullptr, a));
-    if (pool) {
-      GI_TRY(act_bwd(st, true, v->gbuf[cur ^ 1], v->ga[below], nullptr, v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
-    } else {
-      cur ^= 1;
-      if (!a.mask || !a.mask_applied) GI_TRY(act_bwd(st, false, v->gbuf[cur], v->ga[below], seed_of(below), v->gbuf[cur], n, Hl[below], Wl[below], kCout[below], !last));
-    }
-    if (last) return readback(v->gbuf[cur], below);
-  }
-  return conv1_adjoint(st, v->gbuf[cur], v->w1, v->sc, gscale, grad_out, n, v->H, v->W);
 }
 
 }  // namespace
@@ -989,7 +674,9 @@ int gi_vgg19_create(gi_ctx* ctx, int H, int W, int max_pairs, gi_vgg** out) {
              H, W);
   gi_vgg* v = new (std::nothrow) gi_vgg();
   GI_REQUIRE(v, "vgg19_create: out of host memory");
-  v->ctx = ctx; v->H = H; v->W = W; v->max_pairs = max_pairs;
+  v->ctx = ctx;
+  v->t.nconv = NCONV; v->t.cin = kCin; v->t.cout = kCout; v->t.tap_after = kTapAfter; v->t.pool_after = kPoolAfter;
+  v->t.H = H; v->t.W = W; v->t.max_pairs = max_pairs;
   int64_t off = 0;
   for (int i = 0; i < NCONV; ++i) {
     v->woff[i] = off; off += (int64_t)kCout[i] * kCin[i] * 9;
@@ -1030,10 +717,10 @@ int gi_vgg19_bind(gi_vgg* v, const float* params, void* ws, int64_t ws_bytes) {
 int gi_vgg19_sync_weights(gi_vgg* v) {
   GI_REQUIRE(v && v->bound, "vgg19_sync_weights: not bound");
   hipStream_t st = v->ctx->stream;
-  GI_TRY(sum_cin(st, v->params + v->woff[0], v->w1));
+  GI_TRY(sum_cin(st, v->params + v->woff[0], v->t.w1));
   for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, false, v->params + v->woff[i], v->wpk[i], kCout[i], kCin[i]));
   if (v->gbound) {     // the transposed convolutions' weights, only for a handle that can run the backward
-    for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, true, v->params + v->woff[i], v->wT[i], kCout[i], kCin[i]));
+    for (int i = 1; i < NCONV; ++i) GI_TRY(pack3x3(st, true, v->params + v->woff[i], v->t.wT[i], kCout[i], kCin[i]));
   }
   v->synced = true;
   return GI_OK;
@@ -1042,7 +729,7 @@ int gi_vgg19_sync_weights(gi_vgg* v) {
 int gi_vgg19_perceptual_style(gi_vgg* v, const float* output, const float* target, int n, float weight_p, float weight_s, float* out2,
                               float* per_tap10) {
   GI_REQUIRE(v && v->bound && v->synced, "vgg19_perceptual_style: bind + sync_weights first");
-  GI_REQUIRE(output && target && out2 && n > 0 && n <= v->max_pairs, "vgg19_perceptual_style: n=%d (max %d)", n, v->max_pairs);
+  GI_REQUIRE(output && target && out2 && n > 0 && n <= v->t.max_pairs, "vgg19_perceptual_style: n=%d (max %d)", n, v->t.max_pairs);
   GI_TRY(vgg_run(v, output, target, n, -1, nullptr));
   GI_TRY(finish_terms(v->ctx->stream, v->partial, v->fin, v->per_tap, weight_p, weight_s, out2));
   if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, v->ctx->stream));
@@ -1066,7 +753,7 @@ int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* 
                                    float* per_tap10, float* grad_out, float gscale) {
   GI_REQUIRE(v && v->gbound, "vgg19_perceptual_style_grad: no grad workspace bound (gi_vgg19_bind_grad)");
   GI_REQUIRE(v->bound && v->synced, "vgg19_perceptual_style_grad: bind + sync_weights first");
-  GI_REQUIRE(output && target && out2 && grad_out && n > 0 && n <= v->max_pairs, "vgg19_perceptual_style_grad: n=%d (max %d)", n, v->max_pairs);
+  GI_REQUIRE(output && target && out2 && grad_out && n > 0 && n <= v->t.max_pairs, "vgg19_perceptual_style_grad: n=%d (max %d)", n, v->t.max_pairs);
   hipStream_t st = v->ctx->stream;
   v->grad_n = 0;
   GI_HIP(hipMemsetAsync(v->amax, 0, 256, st));
@@ -1075,8 +762,7 @@ int gi_vgg19_perceptual_style_grad(gi_vgg* v, const float* output, const float* 
   if (per_tap10) GI_HIP(hipMemcpyAsync(per_tap10, v->per_tap, 10 * sizeof(float), hipMemcpyDeviceToDevice, st));
   GI_TRY(vgg_seeds(v, n, weight_p, weight_s));
   v->grad_n = n;
-  GI_TRY(vgg_backward(v, n, -1, nullptr, grad_out, gscale));
-  return GI_OK;
+  return trunk_backward(v->t, st, n, -1, nullptr, grad_out, gscale);
 }
 
 int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw) {
@@ -1084,13 +770,12 @@ int gi_vgg19_grad_layer(gi_vgg* v, int layer, float* out_nchw) {
   GI_REQUIRE(v->synced && v->grad_n > 0, "vgg19_grad_layer: no gi_vgg19_perceptual_style_grad call to read back");
   GI_REQUIRE(out_nchw && layer >= 0 && layer < NCONV, "vgg19_grad_layer: layer=%d", layer);
   // replays the backward of the last grad call from what it left in the workspace (maps, seeds, scale), down to `layer`
-  GI_TRY(vgg_backward(v, v->grad_n, layer, out_nchw, nullptr, 1.f));
-  return GI_OK;
+  return trunk_backward(v->t, v->ctx->stream, v->grad_n, layer, out_nchw, nullptr, 1.f);
 }
 
 int gi_vgg19_features(gi_vgg* v, const float* x, int n, int tap, float* out_nchw) {
   GI_REQUIRE(v && v->bound && v->synced, "vgg19_features: bind + sync_weights first");
-  GI_REQUIRE(x && out_nchw && n > 0 && n <= v->max_pairs && tap >= 0 && tap < 5, "vgg19_features: n=%d tap=%d", n, tap);
+  GI_REQUIRE(x && out_nchw && n > 0 && n <= v->t.max_pairs && tap >= 0 && tap < 5, "vgg19_features: n=%d tap=%d", n, tap);
   // the runner works on 2n stacked images: feed x twice, return the first n
   GI_TRY(vgg_run(v, x, x, n, tap, out_nchw));
   return GI_OK;
@@ -1167,7 +852,7 @@ int gi_debug_vgg_seed(gi_ctx* ctx, int store, const void* Fo, void* Ft, const fl
 
 int gi_debug_vgg_scale(gi_ctx* ctx, const unsigned* smax, float* sc) {
   GI_REQUIRE(ctx && smax && sc, "debug_vgg_scale: null pointer");
-  return seed_scale(ctx->stream, smax, sc);
+  return seed_scale(ctx->stream, smax, sc, 1);
 }
 
 int gi_debug_vgg_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, const void* seed, void* out, int n, int H, int W, int C, int relu) {
@@ -1182,7 +867,7 @@ int gi_debug_vgg_act_bwd(gi_ctx* ctx, int pool, const void* g, const void* act, 
 int gi_debug_vgg_conv1_adjoint(gi_ctx* ctx, const void* D, const float* w1, const float* sc, float gscale, float* dimg, int n, int H, int W) {
   GI_REQUIRE(ctx && D && w1 && sc && dimg, "debug_vgg_conv1_adjoint: null pointer");
   GI_REQUIRE(n > 0 && H > 0 && W > 0 && GI_VGG_FITS31((int64_t)n * H * W * 64), "debug_vgg_conv1_adjoint: n=%d H=%d W=%d", n, H, W);
-  return conv1_adjoint(ctx->stream, (const half_t*)D, w1, sc, gscale, dimg, n, H, W);
+  return conv1_adjoint(ctx->stream, (const half_t*)D, w1, sc + 1, 0, gscale, dimg, n, H, W);
 }
 
 }  // extern "C"

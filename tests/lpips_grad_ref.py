@@ -164,7 +164,7 @@ def stored_seed_bound(fa, fb, lin, s):
 
 
 def pow2_scale(m, exp=-2):
-    """The power of two that puts m > 0 into [2^(exp-1), 2^exp); 1 for m == 0 (lpips_scale_kernel)."""
+    """The power of two that puts m > 0 into [2^(exp-1), 2^exp); 1 for m == 0 (vggtrunk.hip's seed_scale_kernel)."""
     if not m > 0 or not np.isfinite(m):
         return 1.0
     return float(2.0 ** (exp - np.frexp(float(m))[1]))
@@ -172,7 +172,7 @@ def pow2_scale(m, exp=-2):
 
 # ---- activation backward -----------------------------------------------------------------------------------------------------------
 def act_bwd_emulate(g, act, seed, pool, relu=True):
-    """lpips_act_bwd_kernel bit for bit, NCHW float16 tensors in, float16 out: one fp16 rounding of [act > 0] (routed g + seed) in fp32.
+    """vggtrunk.hip's act_bwd_kernel bit for bit, NCHW float16 tensors in, float16 out: one fp16 rounding of [act > 0] (routed g + seed) in fp32.
     pool: g is (n,C,H/2,W/2) and goes to the first maximum of each 2x2 window of act in row-major order."""
     act = act.float()
     n, C, H, W = act.shape
@@ -214,7 +214,7 @@ def conv1_adjoint_emulate(wA, D, mul):
 
 
 def pack_t(w):
-    """[cout][cin][3][3] float32 -> float16 [cin][8 - tap][cout] (lpips_pack3x3_t_kernel)."""
+    """[cout][cin][3][3] float32 -> float16 [cin][8 - tap][cout] (vggtrunk.hip's pack3x3_t_kernel)."""
     w = np.asarray(w, np.float32)
     cout, cin = w.shape[:2]
     return np.ascontiguousarray(w.reshape(cout, cin, 9)[:, :, ::-1].transpose(1, 2, 0)).astype(np.float16)

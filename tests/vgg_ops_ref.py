@@ -1,4 +1,4 @@
-"""fp64 restatements of the VGG-19 loss path's kernels (csrc/vgg.hip and the 3x3 mode of the implicit GEMMs), one op each, on exactly
+"""fp64 restatements of the VGG-19 loss path's kernels (csrc/vgg.hip, csrc/vggtrunk.hip and the 3x3 mode of the implicit GEMMs), one op each, on exactly
 the operands the kernel sees: fp16-quantised maps (NHWC), fp32 master weights rounded as the pack kernels round them. Plain torch on
 the CPU; tests/test_vgg_ops_ref_cpu.py proves every one against torch's own operators, autograd and the pinned loss functions of
 oracle.torch_ref, tests/test_vgg_ops_gpu.py holds the kernels to them through the gi_debug_vgg_* entries."""
@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 F64 = torch.float64
-SEED_EXP = -2            # kSeedExp (csrc/vgg.hip)
+SEED_EXP = -2            # kSeedExp (csrc/vggtrunk.hip)
 SEED_SAMPLE_ALL = 8      # kSeedSampleAll: maps of more 256-pixel blocks are sampled by the maximum pass
 
 
@@ -140,7 +140,7 @@ def maxpool2(x):
 
 
 def pool_bwd(g, act, relu):
-    """vgg_act_bwd_kernel<true>: g (n,H/2,W/2,C) goes to the FIRST maximum of every window of act, times [max > 0] when relu"""
+    """vggtrunk.hip's act_bwd_kernel<true> with no seed: g (n,H/2,W/2,C) goes to the FIRST maximum of every window of act, times [max > 0] when relu"""
     wa = _windows(act.to(F64))
     m = wa.amax(3, keepdim=True)
     first = (wa == m).to(torch.int8).argmax(3, keepdim=True)              # argmax of a 0/1 tensor: the first 1
@@ -152,7 +152,7 @@ def pool_bwd(g, act, relu):
 
 
 def act_bwd(g, act, seed, relu):
-    """vgg_act_bwd_kernel<false>: [act > 0 or not relu] * fp16(fp32(g) + fp32(seed)); g / seed None: zeros"""
+    """vggtrunk.hip's act_bwd_kernel<false>: [act > 0 or not relu] * fp16(fp32(g) + fp32(seed)); g / seed None: zeros"""
     z = torch.zeros(act.shape, dtype=torch.float32)
     s = ((z if g is None else g.float()) + (z if seed is None else seed.float())).to(torch.float16).to(F64)
     return torch.where(act > 0, s, torch.zeros_like(s)) if relu else s
@@ -215,7 +215,7 @@ def sampled_mask(HW):
 
 
 def scale(am):
-    """vgg_scale_kernel: s = 2^(SEED_EXP - e), max |seed| = m 2^e; zero, inf, NaN: 1; the exponent clamped to +-100"""
+    """vggtrunk.hip's seed_scale_kernel with n = 1: s = 2^(SEED_EXP - e), max |seed| = m 2^e; zero, inf, NaN: 1; the exponent clamped to +-100"""
     if not (am > 0.0 and am < math.inf):
         return 1.0
     k = SEED_EXP - math.frexp(am)[1]

@@ -4,9 +4,8 @@
   python tools/time_lpips.py [--size 256] [--n 32] [--reps 100] [--cpu-pairs 4] [--out FILE.json]
       LPIPS.distance on n pairs of size x size images (max_pairs = n: one call of the handle), HIP events, the median of --reps
       after warm-up; then the torch fp32 restatement of the same metric on 16 host threads of the same box.
-  GI_LIB_PATH=<unfused build> python tools/time_lpips.py ...
-      the same numbers from another build of the library. The A/B of the fused tap + pool kernel is a build with -DGI_LPIPS_UNFUSED
-      (separate distance and pooling passes):  GI_OUT=../libganinpaint_unfused.so GI_BUILD_DIR=build_unfused csrc/build.sh -DGI_LPIPS_UNFUSED"""
+  GI_LIB_PATH=<another build> python tools/time_lpips.py ...
+      the same numbers from another build of the library."""
 import argparse
 import json
 import os
